@@ -313,9 +313,6 @@ __global__ __launch_bounds__(256) void csr_gather_banded64(const int32_t *__rest
 // neighbour within kBandMax rows
 bool banded_ok(const athena_mp_graph *g, bool transposed, int F, int64_t ldx, int64_t ldy, const float *x, const float *y)
 {
-#ifdef AGG_NO_BANDED
-    return false;
-#endif
     return g->band <= kBandMax && g->n_rows == g->n_cols && (F == 64 || F == 128) && ldx >= F && ldx % 4 == 0 && ldx <= 1024 &&
            ldy >= F && ldy % 4 == 0 && ldy <= 1024 && (transposed ? g->max_col_len : g->max_row_len) <= kBandEntries &&
            (uintptr_t)x % 16 == 0 && (uintptr_t)y % 16 == 0;

@@ -21,11 +21,6 @@
 
 #include "common.h"
 
-#ifndef DUV_VARIANT
-#define DUV_VARIANT 0   // timing-only diagnostic builds (scripts/build_variants.sh), never shipped: bit mask
-                        // 1 no matrix work | 2 no row loads | 4 no stores | 8 no activation / divisor
-#endif
-
 namespace {
 
 typedef float v4f __attribute__((ext_vector_type(4)));
@@ -79,7 +74,7 @@ __device__ __forceinline__ v4f div4(v4f x, float d, float inv)
     return v4f{lo[0], lo[1], hi[0], hi[1]};
 }
 
-// Round 3 -- what bounded round 2's kernels, measured with timing-only builds (DUV_VARIANT): memory path alone (row
+// Round 3 -- what bounded round 2's kernels, measured with timing-only builds: memory path alone (row
 // loads + epilogue + stores, no matrix work) 0.29 ms, matrix work without the row loads 0.28 ms, together 0.39 ms.  The
 // memory path was slow because every lane read and wrote its vertex row 16 bytes at a time in the MFMA operand layout
 // (lane (v, q) <-> a[v, 16 j + 4 q ..]): the 16 lanes the address unit takes together touched 16 different rows, so
@@ -169,11 +164,7 @@ __global__ __launch_bounds__(256) void duv_rows_any_kernel(BucketSplit sp, const
     auto issue_rows = [&](Stage &s, const Ids &id) {
 #pragma unroll
         for (int k = 0; k < KJ; ++k) {
-#if DUV_VARIANT & 2   // timing-only: no row loads
-            s.x[k] = v4f{1.0f, 2.0f, 3.0f, (float)id.r[k]};
-#else
             s.x[k] = *reinterpret_cast<const v4f *>(X + (int64_t)id.r[k] * K + in_col[k]);
-#endif
         }
     };
     v4f xf[KJ];
@@ -199,12 +190,6 @@ __global__ __launch_bounds__(256) void duv_rows_any_kernel(BucketSplit sp, const
         v4f accs[OT];
 #pragma unroll
         for (int ot = 0; ot < OT; ++ot) accs[ot] = v4f{0.0f, 0.0f, 0.0f, 0.0f};
-#if DUV_VARIANT & 1   // timing-only: no matrix work
-#pragma unroll
-        for (int j = 0; j < KJ; ++j)
-#pragma unroll
-            for (int ot = 0; ot < OT; ++ot) accs[ot] = accs[ot] + xf[j];
-#else
 #pragma unroll
         for (int j = 0; j < KJ; ++j)
 #pragma unroll
@@ -212,9 +197,9 @@ __global__ __launch_bounds__(256) void duv_rows_any_kernel(BucketSplit sp, const
 #pragma unroll
                 for (int ot = 0; ot < OT; ++ot)
                     accs[ot] = __builtin_amdgcn_mfma_f32_16x16x4f32(Wf[ot][j][c], xf[j][c], accs[ot], 0, 0, 0);
-#endif
-        switch ((DUV_VARIANT & 8) ? 99 : act) {   // wave-uniform: one scalar branch per tile, each arm straight-line
-        case 99: break;
+        switch (act) {   // wave-uniform: one scalar branch per tile, each arm straight-line
+        case 99: break;   // never passed (act is an ATHENA_MP_ACT_* value on every path): the case set decides how the switch
+                          // is lowered, and without this arm the register allocation of these kernels changes
         case ATHENA_MP_ACT_SIGMOID: {
             const float cs = -1.4426950408889634f * inv;     // 1 / (1 + 2^(-log2(e) x / d)): the divisor rides in the constant
 #pragma unroll
@@ -252,11 +237,7 @@ __global__ __launch_bounds__(256) void duv_rows_any_kernel(BucketSplit sp, const
 #pragma unroll
         for (int k = 0; k < OT; ++k) {
             const v4f y = *reinterpret_cast<const v4f *>(tout + out_row[k] * PO + out_col[k]);
-#if DUV_VARIANT & 4   // timing-only: no stores (every value stays live)
-            if (y[0] + y[1] + y[2] + y[3] == 12345.678f) Y[gw] = y[0];
-#else
             *reinterpret_cast<v4f *>(Y + (int64_t)orow[k] * NO + out_col[k]) = y;
-#endif
         }
         asm volatile("" ::: "memory");
         turn_in(next);                // tile i+1 (its rows were issued one step ago) takes the operand registers
@@ -525,19 +506,12 @@ __global__ __launch_bounds__(256, (OT > 5 ? 1 : 2)) void duv_rows_wide_kernel(Bu
         for (int u = 0; u < TI; ++u) id.t[u] = trows[tb + ti.row[u]];
     };
     auto issue_rows = [&](Stage &s, const Ids &id) {
-#if DUV_VARIANT & 2   // timing-only: no row loads
-#pragma unroll
-        for (int i = 0; i < 4; ++i) s.f[i] = v4f{1.0f, 2.0f, 3.0f, (float)id.f[i]};
-#pragma unroll
-        for (int u = 0; u < TI; ++u) s.t[u] = v4f{1.0f, 2.0f, 3.0f, (float)id.t[u]};
-#else
 #pragma unroll
         for (int i = 0; i < 4; ++i) s.f[i] = *reinterpret_cast<const v4f *>(X + (int64_t)id.f[i] * xpm + 4 * n);
 #pragma unroll
         for (int u = 0; u < TI; ++u)   // (a lane without a tail chunk repeats chunk 0 of row 0 -- column 0: the main part)
             s.t[u] = XS ? *reinterpret_cast<const v4f *>((ti.col[u] >= 64 ? xt + (int64_t)id.t[u] * xpt : X + (int64_t)id.t[u] * xpm) + ti.col[u])
                         : *reinterpret_cast<const v4f *>(X + (int64_t)id.t[u] * K + ti.col[u]);
-#endif
     };
     v4f xf[KJ];
     auto turn_in = [&](const Stage &s) {     // coalesced registers -> LDS tile -> operand layout (lane (v, q): a[v, 16 j + 4 q ..])
@@ -574,12 +548,6 @@ __global__ __launch_bounds__(256, (OT > 5 ? 1 : 2)) void duv_rows_wide_kernel(Bu
         v4f accs[OT];
 #pragma unroll
         for (int ot = 0; ot < OT; ++ot) accs[ot] = v4f{0.0f, 0.0f, 0.0f, 0.0f};
-#if DUV_VARIANT & 1   // timing-only: no matrix work
-#pragma unroll
-        for (int j = 0; j < KJ; ++j)
-#pragma unroll
-            for (int ot = 0; ot < OT; ++ot) accs[ot] = accs[ot] + xf[j];
-#else
 #pragma unroll
         for (int j = 0; j < KJ; ++j)
 #pragma unroll
@@ -587,9 +555,8 @@ __global__ __launch_bounds__(256, (OT > 5 ? 1 : 2)) void duv_rows_wide_kernel(Bu
 #pragma unroll
                 for (int ot = 0; ot < OT; ++ot)
                     accs[ot] = __builtin_amdgcn_mfma_f32_16x16x4f32(Wf[ot][j][c], xf[j][c], accs[ot], 0, 0, 0);
-#endif
-        switch ((DUV_VARIANT & 8) ? 99 : act) {   // wave-uniform: one scalar branch per tile, each arm straight-line
-        case 99: break;
+        switch (act) {   // wave-uniform: one scalar branch per tile, each arm straight-line
+        case 99: break;   // never passed: kept for the lowering, as in duv_rows_any_kernel
         case ATHENA_MP_ACT_SIGMOID: {
             const float cs = -1.4426950408889634f * inv;     // 1 / (1 + 2^(-log2(e) x / d)): the divisor rides in the constant
 #pragma unroll
@@ -665,11 +632,7 @@ __global__ __launch_bounds__(256, (OT > 5 ? 1 : 2)) void duv_rows_wide_kernel(Bu
                                 : *reinterpret_cast<const v4f *>(tout + to.row[k < 4 ? 0 : k - 4] * PO + to.col[k < 4 ? 0 : k - 4]);
             float *dst = k < 4 ? Y + (int64_t)orow[k < 4 ? k : 0] * NO + 4 * n
                                : Y + (int64_t)otail[k < 4 ? 0 : k - 4] * NO + to.col[k < 4 ? 0 : k - 4];
-#if DUV_VARIANT & 4   // timing-only: no stores (every value stays live)
-            if (y[0] + y[1] + y[2] + y[3] == 12345.678f) Y[gw] = y[0];
-#else
             *reinterpret_cast<v4f *>(dst) = y;
-#endif
         }
         asm volatile("" ::: "memory");
         turn_in(next);                // tile i+1 (its rows were issued one step ago) takes the operand registers
@@ -1043,11 +1006,8 @@ __device__ __forceinline__ float duv_act_back(float y, float g)
     return g;
 }
 
-#ifndef DUV_RO_ATTR
-#define DUV_RO_ATTR
-#endif
 template <int IT, int ACT, bool DIN>
-__global__ __launch_bounds__(256, 1) DUV_RO_ATTR void duv_bwd_ro_kernel(BucketSplit sp, const int32_t *__restrict__ trows,
+__global__ __launch_bounds__(256, 1) void duv_bwd_ro_kernel(BucketSplit sp, const int32_t *__restrict__ trows,
                                                             const int32_t *__restrict__ trows_t, const int32_t *__restrict__ tgid,
                                                             const float *__restrict__ A, int Fi, const float *__restrict__ Z,
                                                             const float *__restrict__ DZ, const float *__restrict__ P,
@@ -1386,14 +1346,10 @@ int launch_rows(const athena_mp_graph *g, const float *X, int K, const float *W,
     if (K >= 64 && NO >= 64) {   // 16+ chunks per row on both sides: the structured numbering (two waves per SIMD at 80 fragments)
         const int32_t *trows_t = g->btile_rows + (size_t)32 * nt;
         const uint32_t p_bytes = ro ? (uint32_t)((size_t)g->n_rows * ro->O * sizeof(float)) : 0u;
-#ifdef DUV_PLAIN_TAIL   // A/B builds (scripts/build_variants.sh ... -DDUV_PLAIN_TAIL=1): the tail fragment in 4 half-empty MFMAs
-        constexpr bool tail2 = false;
-#else
-        constexpr bool tail2 = true;
-#endif
+        // K = 72: the tail fragment in 2 MFMAs, not 4 half-empty ones (A/B in profiles/r06_c3_fwd_tail_ab.txt)
 #define AMP_WIDE(KJ_, OT_)                                                                                            \
     if (kj == KJ_ && ot == OT_) {                                                                                     \
-        if (KJ_ == 5 && OT_ == 4 && K == 72 && tail2) {   /* 72 -> 64 (configs[2]): the tail fragment in 2 MFMAs, all three forms */ \
+        if (KJ_ == 5 && OT_ == 4 && K == 72) {   /* 72 -> 64 (configs[2]): the tail fragment in 2 MFMAs, all three forms */ \
             if constexpr (KJ_ == 5 && OT_ == 4) {                                                                       \
                 if (ro && XT)                                                                                         \
                     hipLaunchKernelGGL((duv_rows_wide_kernel<5, 4, true, true, 2>), grid, dim3(256), 0, amp::stream(), sp, trows_abs, \

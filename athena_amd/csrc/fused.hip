@@ -41,11 +41,10 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // 32-row chunks, one row pair per wave; the first kFirst row loads of the NEXT chunk are issued before
 // the matrix work of the CURRENT chunk and consumed after it.
-#define FUSED_STAGGER 0   // measured at configs[1]: 0.936 / 0.884 ms with, 0.930 / 0.890 ms without (forward / reverse): no gain here
 #define KFIRST 16
 constexpr int kFirst = KFIRST;
 
-#define KIPF_NT 13   // bit mask, A/B in profiles/r04_kipf_nt_ab.txt: nontemporal stores of P (1), of Z (2; 4 = agg_gemm256_kernel's forward launch), nontemporal loads of agg_gemm_kernel's forward-launch entry ids + coefficients (8; the same in agg_gemm256_kernel measured slower, not in the tree)
+// Nontemporal streams, each decided by the A/B in profiles/r04_kipf_nt_ab.txt: noted where they are used.
 template <int N, bool COEF, int ACT, bool BUF>
 __global__ __launch_bounds__(1024) void agg_gemm_kernel(const int32_t *__restrict__ rowptr,
                                                         const int32_t *__restrict__ idx,
@@ -116,8 +115,9 @@ __global__ __launch_bounds__(1024) void agg_gemm_kernel(const int32_t *__restric
         }
         if (gl < len) {
             // (the forward launch reads its 80 MB of entry ids and coefficients nontemporal -- they are used once and would
-            // push rows of X out of the caches: + 1.8 % on it; the coefficient-free reverse launch lost 0.8 % with the same)
-            if constexpr (COEF && (KIPF_NT & 8)) {
+            // push rows of X out of the caches: + 1.8 % on it; the coefficient-free reverse launch lost 0.8 % with the same;
+            // the same in agg_gemm256_kernel measured slower)
+            if constexpr (COEF) {
                 idx0 = __builtin_nontemporal_load(idx + start + gl);
                 c0 = __builtin_nontemporal_load(coef + start + gl);
             } else {
@@ -175,7 +175,7 @@ __global__ __launch_bounds__(1024) void agg_gemm_kernel(const int32_t *__restric
             if (off > 0) {
                 my_idx = -1; my_c = 0.0f;
                 if (off + gl < len) {
-                    if constexpr (COEF && (KIPF_NT & 8)) {
+                    if constexpr (COEF) {
                         my_idx = __builtin_nontemporal_load(idx + start + off + gl);
                         my_c = __builtin_nontemporal_load(coef + start + off + gl);
                     } else {
@@ -214,13 +214,8 @@ __global__ __launch_bounds__(1024) void agg_gemm_kernel(const int32_t *__restric
     auto store_row = [&](int64_t chunk, int buf, const v4f &acc) {
         const int64_t row = chunk * CH + lrow;
         *reinterpret_cast<v4f *>(Ts + (buf * CH + lrow) * LD + 4 * gl) = acc;
-        if (P != nullptr && chunk < n_chunks && row < n_rows) {
-#if KIPF_NT & 1
+        if (P != nullptr && chunk < n_chunks && row < n_rows)   // P (written once, streamed once by dW) nontemporal: - 0.6 % on the step
             __builtin_nontemporal_store(acc, reinterpret_cast<v4f *>(P + row * K + 4 * gl));
-#else
-            *reinterpret_cast<v4f *>(P + row * K + 4 * gl) = acc;
-#endif
-        }
     };
 
     // (Measured and dropped: walking the rows longest first so that the rows of a chunk have equal lengths -- 6 % slower,
@@ -264,28 +259,13 @@ __global__ __launch_bounds__(1024) void agg_gemm_kernel(const int32_t *__restric
             const int64_t row0 = chunk * CH + 16 * rb + 4 * g4;   // C/D: col = lane&15, row = 4*(lane>>4) + reg
             const int col = 16 * ct + l15;
 #pragma unroll
-            for (int r = 0; r < 4; ++r)
-                if (row0 + r < n_rows) {
-#if KIPF_NT & 2
-                    __builtin_nontemporal_store(act_f<ACT>(c[r] + bv), &Z[(row0 + r) * N + col]);
-#else
-                    Z[(row0 + r) * N + col] = act_f<ACT>(c[r] + bv);
-#endif
-                }
+            for (int r = 0; r < 4; ++r)   // (Z's 4-byte-per-lane stores gain nothing from nontemporal)
+                if (row0 + r < n_rows) Z[(row0 + r) * N + col] = act_f<ACT>(c[r] + bv);
         };
-#if FUSED_STAGGER
-        // Between two barriers a wave has two independent jobs: the matrix work of chunk k0 (reads tile `buf`) and the
-        // gather of its rows of chunk k1 (writes tile `buf ^ 1`).  Waves 4-7 and 12-15 run them in the opposite order, so
-        // every SIMD holds two waves on the matrix pipe and two waiting for rows instead of four doing the same thing.
-        if ((wave >> 2) & 1) {
-            store_row(k1, buf ^ 1, finish());
-            matrix_work();
-        } else
-#endif
-        {
-            matrix_work();
-            store_row(k1, buf ^ 1, finish());
-        }
+        // (Measured and dropped: waves 4-7 and 12-15 gathering chunk k1 before the matrix work of k0, so that every SIMD holds
+        // two waves on each job -- configs[1] 0.936 / 0.884 ms with, 0.930 / 0.890 ms without (forward / reverse).)
+        matrix_work();
+        store_row(k1, buf ^ 1, finish());
         load_state(k2);
         if (tid == 0) s_ticket[it & 1] = draw();
         __syncthreads();
@@ -493,13 +473,8 @@ __global__ __launch_bounds__(512) void agg_gemm256_kernel(const int32_t *__restr
             const int lrow = 2 * wave + r;
             const int64_t row = chunk * CH + lrow;
             *reinterpret_cast<v4f *>(Ts + (buf * CH + lrow) * LD + 4 * lane) = acc[r];
-            if (P != nullptr && chunk < n_chunks && row < n_rows) {
-#if KIPF_NT & 1
+            if (P != nullptr && chunk < n_chunks && row < n_rows)   // P nontemporal: forward - 2.4 % at configs[4]
                 __builtin_nontemporal_store(acc[r], reinterpret_cast<v4f *>(P + row * K + 4 * lane));
-#else
-                *reinterpret_cast<v4f *>(P + row * K + 4 * lane) = acc[r];
-#endif
-            }
         }
     };
     auto matrix_work = [&](int64_t chunk, int buf) {     // this wave's two 16x16 blocks of the chunk's [16 x 256] output
@@ -523,7 +498,7 @@ __global__ __launch_bounds__(512) void agg_gemm256_kernel(const int32_t *__restr
             if (row0 + r < n_rows) {
                 // (the forward launch -- the one that also keeps P -- streams Z out nontemporal: - 1.4 % on it at configs[4];
                 // the reverse launch, whose output the next layer's reverse reads, does not: + 0.7 % there)
-                if ((KIPF_NT & 4) && P != nullptr) {
+                if (P != nullptr) {
                     __builtin_nontemporal_store(act_f<ACT>(ca[r] + bv[0]), &Z[(row0 + r) * N + n0 + l15]);
                     __builtin_nontemporal_store(act_f<ACT>(cb[r] + bv[1]), &Z[(row0 + r) * N + n0 + 16 + l15]);
                 } else {
@@ -640,16 +615,10 @@ int athena_mp_kipf_layer_fwd(const athena_mp_graph *g, int32_t Fi, int32_t Fo, c
     AMP_REQUIRE(x && W && Z, "kipf_layer_fwd: null tensor");
     // hub rows (> kLongRow entries) would stall a whole workgroup at the chunk barrier: such graphs take
     // the two-kernel route, whose aggregation splits them into parallel segments
-#ifndef KIPF_LAYER_BANDED
-#define KIPF_LAYER_BANDED 1   // A/B builds: 0 = block-diagonal batches through the one-launch kernel like every other graph
-#endif
     // a block-diagonal batch of small graphs: the aggregation gathers from LDS (agg.hip, csr_gather_banded64) and the dense step
     // follows as its own launch -- faster than the one launch that chases rows through HBM (profiles/r06_kipf_banded_ab.txt)
-    const bool banded = KIPF_LAYER_BANDED && (Fi == 64 || Fi == 128) && kipf_gather_is_banded(g, false, Fi, x, P ? P : x);
-#ifndef KIPF_BANDED_FUSED
-#define KIPF_BANDED_FUSED 1   // A/B builds: 0 = banded aggregation and dense step as two launches also at 64 -> 64
-#endif
-    if (KIPF_BANDED_FUSED && banded && Fi == 64 && Fo == 64) {   // ... in ONE launch: P goes from LDS into the dense step (banded_fused.hip)
+    const bool banded = (Fi == 64 || Fi == 128) && kipf_gather_is_banded(g, false, Fi, x, P ? P : x);
+    if (banded && Fi == 64 && Fo == 64) {   // ... in ONE launch: P goes from LDS into the dense step (banded_fused.hip; same A/B file)
         const int rc = banded_agg_gemm64(g, false, g->coef, x, W, 0, bias, act, P, Z);
         if (rc >= 0) return rc;
     }
@@ -671,8 +640,8 @@ int athena_mp_kipf_layer_bwd_x(const athena_mp_graph *g, int32_t Fi, int32_t Fo,
     AMP_REQUIRE(g && Fi > 0 && Fo > 0, "kipf_layer_bwd_x: bad arguments");
     if (g->n_cols == 0) return 0;
     AMP_REQUIRE(dZ && W && dX, "kipf_layer_bwd_x: null tensor");
-    const bool banded = KIPF_LAYER_BANDED && (Fo == 64 || Fo == 128) && Fo <= Fi && kipf_gather_is_banded(g, true, Fo, dZ, dZ);
-    if (KIPF_BANDED_FUSED && banded && Fi == 64 && Fo == 64) {
+    const bool banded = (Fo == 64 || Fo == 128) && Fo <= Fi && kipf_gather_is_banded(g, true, Fo, dZ, dZ);
+    if (banded && Fi == 64 && Fo == 64) {
         const int rc = banded_agg_gemm64(g, true, exact ? g->t_coef : nullptr, dZ, W, 1, nullptr, ATHENA_MP_ACT_NONE, nullptr, dX);
         if (rc >= 0) return rc;
     }

@@ -28,7 +28,7 @@
 // does buy: no P tensor kept per layer (0.5 GB at configs[1]) and one launch fewer.  An 8-wave form (DW_WAVES=8, 256
 // registers, 12-16 rows prefetched per row) measured 1.39-1.43 ms: with two waves per SIMD the matrix work and the row
 // loads do not overlap at all.  Staggering the two jobs of a wave by wave number (waves 4-7, 12-15 gather first) took
-// 1.26 -> 1.20 ms and is kept (DW_STAGGER).
+// 1.26 -> 1.20 ms and is kept.
 #include <algorithm>
 
 #include "common.h"
@@ -46,7 +46,6 @@ constexpr int kCH = 32;          // rows per chunk
 constexpr int kFd = KFD;         // row loads per row issued ahead of the matrix work
 constexpr int kTd = 4;           // entries per row per round beyond them
 
-#define DW_STAGGER 1
 #define DW_WAVES 16
 constexpr int kNW = DW_WAVES;                  // waves per workgroup: 16 (one row pair, one dX block, 4 dW tiles per wave;
                                                // 128 registers) or 8 (two pairs, two blocks, 8 tiles; 256 registers)
@@ -269,16 +268,13 @@ __global__ __launch_bounds__(64 * kNW) void agg_gemm_dw_kernel(const int32_t *__
     for (int it = 0; k0 < n_chunks; ++it) {
         const int buf = it & 1;
         issue_first();                                      // rows of k1 fly under the matrix work of k0
-#if DW_STAGGER
         // Between two barriers a wave has two independent jobs (matrix work on tile `buf`, gather into `buf ^ 1`).
         // Waves 4-7 and 12-15 run them in the opposite order: each SIMD then holds two waves on the matrix pipe and two
         // waiting for rows, instead of all four queueing for the pipe and then all four waiting on memory.
         if ((wave >> 2) & 1) {
             store_rows(k1, buf ^ 1);
             matrix_work(k0, buf);
-        } else
-#endif
-        {
+        } else {
             matrix_work(k0, buf);
             store_rows(k1, buf ^ 1);
         }

@@ -202,19 +202,14 @@ __global__ __launch_bounds__(256) void gno_outer_mfma_kernel(const int32_t *__re
 // The per-wave partial sums are added through LDS in wave order (deterministic).
 typedef float v4f_g __attribute__((ext_vector_type(4)));
 typedef unsigned int v4u_g __attribute__((ext_vector_type(4)));
-// how gno_pc_kernel<true> writes the S it keeps: 0 nontemporal global stores, 1 plain stores, 2 buffer stores with the cache
-// bits GNO_SAVE_AUX (1 sc0, 2 nt, 16 sc1), 3 none (timing only).  configs[3], ms per launch, two runs each on one box
-// (scripts/gpu_keeps_ab.sh): plain 14.65 / 14.74, nt global 14.21 / 14.28, buffer nt 14.05 / 14.08, buffer sc0 sc1 nt 14.07 / 14.09,
-// buffer sc0 sc1 14.39 / 14.40, none 11.88 / 11.89 (= the kernel without the copy: the LDS reads of the copy cost nothing,
-// the 33 GB of writes make the launch HBM bound: 63 GB in 14.05 ms = 4.5 TB/s)
-#define GNO_SAVE_MODE 2
-#define GNO_PX_NT_LOAD 1   // gno_px_gather_kernel reads the partials (15 GB, read once) with nontemporal loads: A/B in profiles/r04_c4_px_store_ab.txt
+// gno_pc_kernel<true> writes the S it keeps with buffer stores, cache bits GNO_SAVE_AUX (1 sc0, 2 nt, 16 sc1).  Measured at
+// configs[3], ms per launch, two runs each on one box (profiles/r03_c4_keep_s_ab.txt): plain stores 14.65 / 14.74, nt global
+// stores 14.21 / 14.28, buffer nt 14.05 / 14.08, buffer sc0 sc1 nt 14.07 / 14.09, buffer sc0 sc1 14.39 / 14.40, no stores
+// (timing only) 11.88 / 11.89 (= the kernel without the copy: the LDS reads of the copy cost nothing, the 33 GB of writes
+// make the launch HBM bound: 63 GB in 14.05 ms = 4.5 TB/s)
 #define GNO_PX_RB_AUX 0   // cache bits of the read-back of the kh = 0 partial (2 = nt: A/B in profiles/r04_c4_px_one_array_ab.txt)
 #define GNO_PX_AUX 0   // cache bits of the per-entry partials' stores (1 sc0, 2 nt, 16 sc1): none -- A/B in profiles/r04_c4_px_one_array_ab.txt
 #define GNO_SAVE_AUX 2
-#ifndef GNO_FV
-#define GNO_FV 0   // timing-only variants (scripts/build_variants.sh), bit mask: 1 no sparse loop, 2 no V loads, 4 no S reads, 8 no contraction, 16 no cross-wave reduction (gno_fused_kernel); 32 idle producers, 64 idle consumers, 8192 half the gathers (gno_pc_kernel); 16384 gno_px_gather_kernel reads the partials as one stream
-#endif
 constexpr int kGF = 64, kGH = 64, kGRows = 16, kGSP = 33 * kGF + 4;   // LDS row pitch of S_half
 
 __global__ __launch_bounds__(1024) void gno_fused_kernel(const int32_t *__restrict__ rowptr,
@@ -275,7 +270,7 @@ __global__ __launch_bounds__(1024) void gno_fused_kernel(const int32_t *__restri
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[b][r] = 0.0f;
             float sb[2] = {0.0f, 0.0f};
-            for (int wb = cw0; wb < ((GNO_FV & 1) ? cw0 : cw1); wb += 64) {
+            for (int wb = cw0; wb < cw1; wb += 64) {
                 const int nb = min(64, cw1 - wb);
                 int bj = cj, be = ce;
                 if (wb != cw0) {   // rows longer than 64 entries: later blocks are fetched here
@@ -345,23 +340,13 @@ __global__ __launch_bounds__(1024) void gno_fused_kernel(const int32_t *__restri
             const float *ap = vbase + (size_t)(4 * s_beg + g) * kGF + 4 * n;
             const float *bp = sl + 4 * s_beg;
 #pragma unroll 1
-            for (int r = 0; r < ((GNO_FV & 8) ? 0 : 4); ++r) {
+            for (int r = 0; r < 4; ++r) {
                 v4f_g a[UN];
                 float b[UN];
 #pragma unroll
                 for (int u = 0; u < UN; ++u) {
-#if GNO_FV & 2
-                    a[u] = v4f_g{(float)u, (float)r, (float)lane, 1.0f};
-                    asm volatile("" : "+v"(a[u]));
-#else
                     a[u] = *reinterpret_cast<const v4f_g *>(ap + (size_t)u * 4 * kGF);
-#endif
-#if GNO_FV & 4
-                    b[u] = (float)(u + r);
-                    asm volatile("" : "+v"(b[u]));
-#else
                     b[u] = bp[4 * u];
-#endif
                 }
 #pragma unroll
                 for (int u = 0; u < UN; ++u)
@@ -391,7 +376,7 @@ __global__ __launch_bounds__(1024) void gno_fused_kernel(const int32_t *__restri
             const int t = threadIdx.x;                 // 1024 threads = 16 vertices x 64 outputs
             float sum = red[t];
 #pragma unroll
-            for (int w = 1; w < ((GNO_FV & 16) ? 1 : 16); ++w) sum = sum + red[(size_t)w * kGRows * kGF + t];
+            for (int w = 1; w < 16; ++w) sum = sum + red[(size_t)w * kGRows * kGF + t];
             const int v = t >> 6;
             if (r0 + v < n_rows) out[(size_t)perm[r0 + v] * kGF + (t & 63)] = sum;
         }
@@ -497,7 +482,7 @@ int launch_gno_fused(const int32_t *rowptr, const int32_t *idx, const int32_t *e
 }
 
 // ---- producer / consumer form of the fused aggregate (same shapes; d <= 3) -------------------------------------
-// Timing splits of gno_fused_kernel at C4 (GNO_FV builds, profiles/r02_c4_gno_variants.txt): its sparse loop costs
+// Timing splits of gno_fused_kernel at C4 (timing-only builds, profiles/r02_c4_gno_variants.txt): its sparse loop costs
 // 5.2 ms, its contraction 8.1 ms on the matrix pipe alone (+1.8 ms of exposed V loads), the skeleton 2 ms -- and they ADD
 // (17.2 ms), because every wave of the one resident workgroup is in the same phase.  Here the two phases run side by
 // side in one 16-wave workgroup that owns 32 vertices per tile:
@@ -842,14 +827,12 @@ __global__ __launch_bounds__(kPcThreads) void gno_pc_kernel(const int32_t *__res
                 // (tiles hold vertices of nearly equal length, so the shorter rows' extra steps -- on zeros -- are few)
                 auto four = [&](auto K, auto FILL) {
 #pragma unroll
-                    for (int vi = 0; vi < ((GNO_FV & 32) ? 0 : 4); ++vi) {
+                    for (int vi = 0; vi < 4; ++vi) {
                         v4f_g acc[2];
                         float bs;
                         if (vi < kHCache) P.compute<decltype(K)::value, decltype(FILL)::value ? 1 : 2>(LS[vi], CV[vi], ub0, ub1, acc, bs, HCc[vi]);
                         else P.compute<decltype(K)::value>(LS[vi], CV[vi], ub0, ub1, acc, bs);
-                        // (GNO_FV & 8192, timing only: no gathers during pieces 3 .. 6 -- what the launch costs when a feature quarter
-                        // is gathered once per tile instead of once per kh; the results are wrong)
-                        if (!(GNO_FV & 8192) || pc < 3 || pc == 7) P.issue(LS[vi], pJ0, pJ1, vi, cn, second);
+                        P.issue(LS[vi], pJ0, pJ1, vi, cn, second);
                         if (last) P.load_cv(CV[vi], nxt.E0, nxt.E1, vi);
                         const int v = 4 * p + vi;
                         float *srow = buf + (size_t)v * kPPitch;
@@ -945,7 +928,7 @@ __global__ __launch_bounds__(kPcThreads) void gno_pc_kernel(const int32_t *__res
                 const float *vp = vw + (size_t)pc * kPiece;
                 const float *vnext = pc < 7 ? vp + kPiece : vbias;   // the piece after this one
 #pragma unroll
-                for (int rd = 0; rd < ((GNO_FV & 64) ? 0 : 8); ++rd) {
+                for (int rd = 0; rd < 8; ++rd) {
                     v4f_g b0[4], b1[4], an[4];
 #pragma unroll
                     for (int u = 0; u < 4; ++u) {
@@ -968,9 +951,8 @@ __global__ __launch_bounds__(kPcThreads) void gno_pc_kernel(const int32_t *__res
                     if constexpr (SAVE) {
                         if (rd >= 6) {   // this wave's quarter of the piece: slots 8 ot + 4 (rd - 6) .. + 3, 2 KB each
                             const float *src = Sbuf + (size_t)((ti * 8 + pc) & 1) * kPV * kPPitch + 4 * lane;
-                            float *dst = save + (size_t)tile * kSaveTile + (size_t)pc * kSavePiece + 4 * lane;
                             // (a descriptor per tile: the 33 GB lie beyond what one descriptor addresses)
-                            [[maybe_unused]] const __amdgpu_buffer_rsrc_t srs = __builtin_amdgcn_make_buffer_rsrc(
+                            const __amdgpu_buffer_rsrc_t srs = __builtin_amdgcn_make_buffer_rsrc(
                                 (void *)(save + (size_t)tile * kSaveTile), 0, (int)(kSaveTile * 4), 0x00020000);
                             v4f_g cp[8];
 #pragma unroll
@@ -981,17 +963,8 @@ __global__ __launch_bounds__(kPcThreads) void gno_pc_kernel(const int32_t *__res
 #pragma unroll
                             for (int i = 0; i < 8; ++i) {
                                 const int v = 8 * ot + 4 * (rd - 6) + (i >> 1);
-#if GNO_SAVE_MODE == 0
-                                __builtin_nontemporal_store(cp[i], reinterpret_cast<v4f_g *>(dst + (size_t)v * 512 + 256 * (i & 1)));
-#elif GNO_SAVE_MODE == 1
-                                *reinterpret_cast<v4f_g *>(dst + (size_t)v * 512 + 256 * (i & 1)) = cp[i];
-#elif GNO_SAVE_MODE == 3
-                                (void)dst;
-                                asm volatile("" ::"v"(cp[i]));
-#else
                                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u_g, cp[i]), srs,
                                     (int)(((size_t)pc * kSavePiece + (size_t)v * 512 + 256 * (i & 1) + 4 * lane) * 4), 0, GNO_SAVE_AUX);
-#endif
                             }
                         }
                     }
@@ -1650,9 +1623,6 @@ int launch_outer(const int32_t *rowptr, const int32_t *idx, const int32_t *eidx,
 //            32x32x2 MFMAs (B operand read from LDS as it is needed), relu' mask in the C layout, then the
 //            second MFMA that accumulates dU^T / db_u over all entries of all of the wave's vertices.
 // One slab of (H d + H) partial sums per wave, reduced in fixed order by slab_reduce (no atomics).
-#ifndef GDH_VARIANT
-#define GDH_VARIANT 0   // 1: no phase A, 2: no phase B, 3: phase A without its LDS stores -- timing-only builds, never shipped
-#endif
 constexpr int kDRow = 68;                       // LDS pitch of one (vertex, kl) row of 64 q
 constexpr int kDVtx = 32 * kDRow + 4;           // LDS pitch of one vertex' half
 
@@ -1723,7 +1693,7 @@ __global__ __launch_bounds__(1024) void gno_gdh_kernel(const int32_t *__restrict
                 }
             }
 #pragma unroll 1
-            for (int b = 0; b < (GDH_VARIANT == 1 ? 0 : 2); ++b) {
+            for (int b = 0; b < 2; ++b) {
                 const int kl = 2 * wave + b;
                 v4f_g om[4];
 #pragma unroll
@@ -1743,9 +1713,7 @@ __global__ __launch_bounds__(1024) void gno_gdh_kernel(const int32_t *__restrict
                 // lane (vertex m, gq): om[c][r] = G[vertex][kl][q = 16 gq + 4 r + c]
                 float *dst = Gs + (size_t)m * kDVtx + kl * kDRow + 16 * gq;
 #pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    if (GDH_VARIANT != 3 || om[0][r] == 12345.0f)
-                        *reinterpret_cast<v4f_g *>(dst + 4 * r) = v4f_g{om[0][r], om[1][r], om[2][r], om[3][r]};
+                for (int r = 0; r < 4; ++r) *reinterpret_cast<v4f_g *>(dst + 4 * r) = v4f_g{om[0][r], om[1][r], om[2][r], om[3][r]};
             }
             if (half == 1) fetch_ids(tile + gridDim.x);   // flies under the last phase B and the next phase A
             __syncthreads();
@@ -1759,7 +1727,7 @@ __global__ __launch_bounds__(1024) void gno_gdh_kernel(const int32_t *__restrict
                     for (int j = 0; j < 3; ++j) Uk[j] = j < d ? theta[k + (size_t)kGH * j] : 0.0f;
                 }
                 const float *grow = Gs + (size_t)wave * kDVtx + r31 * kDRow + 32 * h;   // G[k = r31][q = 32 h + s]
-                for (int wb = w0; wb < (GDH_VARIANT == 2 ? w0 : w1); wb += 32) {
+                for (int wb = w0; wb < w1; wb += 32) {
                     const int nb = min(32, w1 - wb);
                     int my_j = cj, my_e = ce;
                     if (wb != w0) {   // rows longer than 32 entries: later blocks are fetched here
@@ -2296,13 +2264,10 @@ __global__ void gno_t_entry_kernel(const int32_t *__restrict__ rowptr, const int
     }
 }
 
+// the partials (15 GB, read once) come in with nontemporal loads: A/B in profiles/r04_c4_px_store_ab.txt
 static __device__ __forceinline__ v4f_g px_load(const float *p)
 {
-#if GNO_PX_NT_LOAD
     return __builtin_nontemporal_load(reinterpret_cast<const v4f_g *>(p));
-#else
-    return *reinterpret_cast<const v4f_g *>(p);
-#endif
 }
 
 // dx[u,:] = sum over the transposed row of u of px[w] (64 floats each): 16 lanes x 16 bytes per column,
@@ -2322,11 +2287,6 @@ __global__ __launch_bounds__(256) void gno_px_gather_kernel(const int32_t *__res
         v4f_g pv[8];
 #pragma unroll
         for (int i = 0; i < 8; ++i) w[i] = t_entry[t + i];
-#if GNO_FV & 16384   // timing only: the partials read in the order the transposed CSR lists them (what a segment-ordered emission
-                     // would give the gather: one stream); the sums are wrong
-#pragma unroll
-        for (int i = 0; i < 8; ++i) w[i] = w[i] < 0 ? w[i] : t + i;
-#endif
 #pragma unroll
         for (int i = 0; i < 8; ++i) pv[i] = px_load(px + (size_t)(w[i] < 0 ? 0 : w[i]) * kGF + 4 * l);
 #pragma unroll
