@@ -1008,7 +1008,7 @@ def _make_timed(s, iters):
 
 
 def measure_breakdown(step, iters=5):
-    """Each part of the sharded step timed ALONE (device events, after the timed loop of bench.py): the two halo
+    """Each part of the sharded step timed ALONE (device events, after the timed loop of bench.py --full): the two halo
     exchanges (pack + grouped send/recv + wait), the interior launches and the boundary launches of both passes, the
     dW contraction.  In the step itself the exchanges run under the interior launches; the parts are timed apart so a
     scaling curve can be read (what is communication, what is compute).  Aggregate-first steps only."""

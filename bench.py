@@ -27,9 +27,16 @@ Workloads (--config):
   c4-mesh        BASELINE configs[3] as a LAYER step at any N: graph_nop_layer forward + reverse (aggregation with the kernel
                  MLP, bypass W x + b) on the 2M-point radius mesh numbered in cell order, cut by rows
                  (athena_mp_shard_create_edges); a step = forward + reverse, "edges" = CSR entries.  Not the headline.
-Every line carries "parity": the device results of the LAST timed step against the CPU oracle (N = 1: the whole
-workload; N > 1: sampled rows of every rank + the transported halo rows against the generator); the process exits
-non-zero when parity is above 1e-5 (or P is not bit-exact).
+A plain run does what the headline needs and no more: it sets up, warms up, times the steps, writes --dump-outputs and
+prints the line (`value`, `ms_per_step` and the `roofline` figures the HIP events of the timed loop give).  Everything else
+runs with --full only, after the timed loop:
+  N = 1 (c2, c5)  `parity` of the LAST timed step against the CPU oracle (--cpu-sample-rows: all of c2) and `cpu_baseline`
+                  (the oracle timed, 1 thread); the copy ceiling measured on the device; `relu_epilogue`; and (c2 at its own
+                  size) `secondary`: configs[2], configs[3], configs[4] on one GPU as child processes.
+  N > 1           `parity` (sampled rows of every rank + the transported halo rows against the generator) and `breakdown`
+                  (each part of the step timed alone, incl. roofline.dense).
+  c4-mesh         `parity` against the materialising oracle; `breakdown` at N > 1.
+With --full the process exits non-zero when parity is above 1e-5 (or P is not bit-exact).
 
 --dump-outputs DIR (N = 1): what the LAST timed step handed its caller, as DIR/<name>.npy (c2 / c5: P, Z, dW, dX;
 c4-mesh: out, dX, dtheta, dW, db, dcoords), float32.  Arrays above 4 MB (4e6 bytes) keep a fixed, seeded sample of their rows
@@ -77,13 +84,21 @@ def parse_args():
     ap.add_argument("--cut8", dest="cut", type=float, default=0.05,
                     help="c2-weak-sbm: fraction of undirected pairs crossing partitions at 8 blocks (fixed inter-block "
                          "density; the fraction at N blocks is cut8*(N-1)/7).  -1: structure-free uniform random graph")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU oracle (no cpu_baseline, N=1 parity null)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed loop also run what the headline does not need: parity against the oracle, the CPU "
+                         "baseline, the copy ceiling, the relu epilogue, the `secondary` block (N = 1), the breakdown (N > 1); "
+                         "minutes instead of seconds")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full: skip the CPU oracle (no cpu_baseline, N=1 parity null)")
     ap.add_argument("--cpu-sample-rows", type=int, default=1_000_000,
-                    help="rows of the workload the 1-thread CPU oracle runs (default: all of C2, ~7 s per run)")
-    ap.add_argument("--cpu-runs", type=int, default=5, help="timed runs of the CPU oracle after one warm-up (median reported)")
+                    help="--full: rows of the workload the 1-thread CPU oracle runs (default: all of C2, ~7 s per run)")
+    ap.add_argument("--cpu-runs", type=int, default=5,
+                    help="--full: timed runs of the CPU oracle after one warm-up (median reported)")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="N = 1: skip the `secondary` block (configs[2], configs[3], configs[4] on one GPU; ~2-4 min of child processes)")
-    ap.add_argument("--secondary", default="c3,c4,c5,kb", help="which secondary configurations to run (comma separated)")
+                    help="--full, N = 1: skip the `secondary` block (configs[2], configs[3], configs[4] on one GPU; ~2-4 min of "
+                         "child processes)")
+    ap.add_argument("--secondary", default="c3,c4,c5,kb",
+                    help="--full: which secondary configurations to run (comma separated)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the outputs of the last timed step to DIR/<name>.npy (at most 64 MB; N = 1 only)")
     args = ap.parse_args()
@@ -430,7 +445,8 @@ def run_secondary(which, budget_s=540.0):
 def main_gno(args, world, rank, dev, one_device):
     """--config c4-mesh: graph_nop_layer forward + reverse on the configs[3] mesh, row-partitioned over the ranks
     (dist.GnoShardStep over athena_mp_shard_create_edges).  One json line: whole-job entries/s, the interior forward launch
-    against the fp32-MFMA peak, parity of sampled rows of every rank against the MATERIALISING oracle, the halo's share."""
+    against the fp32-MFMA peak, the halo's share; with --full parity of sampled rows of every rank against the MATERIALISING
+    oracle (parity_gno) and, at N > 1, the breakdown."""
     import contextlib
 
     import numpy as np
@@ -514,8 +530,60 @@ def main_gno(args, world, rank, dev, one_device):
     fwd_ms = float(np.mean([a.elapsed_time(b_) for a, b_ in ev])) if ev else float("nan")
     flops = int_nnz * 2 * H * (Fi + d) + ni * 2 * Fo * (H + 1) * Fi
     tf = flops / (fwd_ms * 1e-3) / 1e12
-    # parity: sampled rows of both blocks of `out` and of dx against the materialising oracle on the compact sub-problem
+    out = {"metric": "msgpass fwd+bwd edges/sec", "value": nnz_total * args.steps / dt, "unit": "edges/s", "n_gpus": world,
+           "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms, "higher_is_better": True,
+           "scaling": "strong" if world > 1 else "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+           "config": {"workload": f"BASELINE configs[3] as a layer step: graph_nop_layer fwd+bwd, radius mesh {N} vertices / {nnz_total} CSR "
+                                  f"entries in cell order, {Fi} features, d = 3, H = {H}, fp32"
+                                  + (f", row-partitioned over {world} GPUs" if world > 1 else ""),
+                      "vertices": N, "entries": nnz_total, "entries_per_gpu": nnz_local, "features": Fi,
+                      "parallelism": f"row-partition x{world}" if world > 1 else "single GPU",
+                      "halo_rows_per_gpu": int(shard.halo_ids.size), "halo_mode": shard.halo_mode,
+                      "halo_fraction": round(float(shard.halo_fraction), 4), "interior_rows_per_gpu": int(ni),
+                      "edge_columns_per_gpu": int(shard.n_edge_cols), "transport": shard.transport, "reverse_pass": step.reverse,
+                      "S_kept_per_block": [t is not None for t in step._s]},
+           "roofline": {"bound": "mfma", "kernel": "gno_pc_kernel<true> (gno_aggregate of rank 0's interior rows, S kept; the halo exchange in flight)",
+                        "achieved": tf, "peak": MFMA_F32_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": tf / MFMA_F32_PEAK_TFLOPS,
+                        "traffic": None, "flops_per_launch": flops, "avg_launch_ms": fwd_ms}}
+    ok = True
+    if args.full:
+        out["parity"] = parity_gno(step, shard, c_loc, theta, w, b, Fi, rank, world, dev, backend, phase)
+        ok = out["parity"]["ok"]
+    if world > 1:
+        if args.full:
+            with phase("breakdown (each part timed alone)", factor=2.0):
+                out["breakdown"] = adist.measure_breakdown_gno(step)
+            out["breakdown"]["note"] = "each part timed alone after the timed loop, rank 0 (events); in the step the exchanges run under the interior work"
+        out["rccl"] = adist.c_comm_stats()      # rank 0's communicator: ranks RCCL itself counts, its version, bytes to every peer
+        out["config"]["control_plane"] = control_plane_note(backend)
+        err = transport_error(str(shard.transport), one_device)
+        if err:
+            out["ok"], out["error"], ok = False, err, False
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    if world > 1:
+        with phase("final barrier"):
+            dist.barrier()
+        watch.close()
+        adist.c_comm_destroy()
+        dist.destroy_process_group()
+    if not ok:
+        sys.exit("bench.py: parity against the oracle FAILED (see the 'parity' object of the line above)")
+
+
+def parity_gno(step, shard, c_loc, theta, w, b, F, rank, world, dev, backend, phase):
+    """--config c4-mesh, --full: sampled rows of both blocks of `out` and of dx of every rank against the materialising oracle on
+    the compact sub-problem, dX also as the reference's scatter over the FORWARD graph, and the transported halo rows against
+    the generator (max over the ranks)"""
+    import numpy as np
+    import torch
+    import torch.distributed as dist
+
+    from athena_amd import synth
     from oracle import oracle
+
+    Fi = Fo = H = F
+    n, ni = shard.n, shard.n_int
     r2 = np.random.default_rng(100 + rank)
     pick = [r2.choice(ni, min(100, ni), replace=False)] if ni else []
     if n - ni:
@@ -601,42 +669,7 @@ def main_gno(args, world, rank, dev, one_device):
               "halo_rows_bit_exact": flags[0] == 0.0, "out_rel": flags[1], "dX_rel": flags[2],
               "dX_rel_vs_scatter_over_the_forward_graph": flags[3], "tol": TOL}
     parity["ok"] = bool(flags[0] == 0.0 and max(flags[1:]) <= TOL)
-    out = {"metric": "msgpass fwd+bwd edges/sec", "value": nnz_total * args.steps / dt, "unit": "edges/s", "n_gpus": world,
-           "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms, "higher_is_better": True,
-           "scaling": "strong" if world > 1 else "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-           "config": {"workload": f"BASELINE configs[3] as a layer step: graph_nop_layer fwd+bwd, radius mesh {N} vertices / {nnz_total} CSR "
-                                  f"entries in cell order, {Fi} features, d = 3, H = {H}, fp32"
-                                  + (f", row-partitioned over {world} GPUs" if world > 1 else ""),
-                      "vertices": N, "entries": nnz_total, "entries_per_gpu": nnz_local, "features": Fi,
-                      "parallelism": f"row-partition x{world}" if world > 1 else "single GPU",
-                      "halo_rows_per_gpu": int(shard.halo_ids.size), "halo_mode": shard.halo_mode,
-                      "halo_fraction": round(float(shard.halo_fraction), 4), "interior_rows_per_gpu": int(ni),
-                      "edge_columns_per_gpu": int(shard.n_edge_cols), "transport": shard.transport, "reverse_pass": step.reverse,
-                      "S_kept_per_block": [t is not None for t in step._s]},
-           "roofline": {"bound": "mfma", "kernel": "gno_pc_kernel<true> (gno_aggregate of rank 0's interior rows, S kept; the halo exchange in flight)",
-                        "achieved": tf, "peak": MFMA_F32_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": tf / MFMA_F32_PEAK_TFLOPS,
-                        "traffic": None, "flops_per_launch": flops, "avg_launch_ms": fwd_ms},
-           "parity": parity}
-    ok = parity["ok"]
-    if world > 1:
-        with phase("breakdown (each part timed alone)", factor=2.0):
-            out["breakdown"] = adist.measure_breakdown_gno(step)
-        out["breakdown"]["note"] = "each part timed alone after the timed loop, rank 0 (events); in the step the exchanges run under the interior work"
-        out["rccl"] = adist.c_comm_stats()      # rank 0's communicator: ranks RCCL itself counts, its version, bytes to every peer
-        out["config"]["control_plane"] = control_plane_note(backend)
-        err = transport_error(str(shard.transport), one_device)
-        if err:
-            out["ok"], out["error"], ok = False, err, False
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    if world > 1:
-        with phase("final barrier"):
-            dist.barrier()
-        watch.close()
-        adist.c_comm_destroy()
-        dist.destroy_process_group()
-    if not ok:
-        sys.exit("bench.py: parity against the oracle FAILED (see the 'parity' object of the line above)")
+    return parity
 
 
 def main():
@@ -852,7 +885,7 @@ def main():
                                       "avg_launch_ms": bw_ms,
                                       "note": "the gathered dZ rows (512 MB) partly live in the 256 MiB Infinity Cache: algorithmic bytes, not HBM bytes"}
     ok = True
-    if world == 1:
+    if world == 1 and args.full:
         try:
             ceil = measure_copy_ceiling(dev)
             out["roofline"]["measured_copy_ceiling_GBps"] = round(ceil, 1)
@@ -869,21 +902,22 @@ def main():
             ok = out["parity"]["ok"]
         else:
             out["parity"] = None
-    else:
-        with phase("parity of every rank against the oracle", factor=3.0):
-            out["parity"] = parity_sharded(shard_step, shard, seeds, dev) if not shard_step.transform_first else None
-        ok = out["parity"] is None or out["parity"]["ok"]
-        with phase("breakdown (each part timed alone)", factor=2.0):
-            out["breakdown"] = adist.measure_breakdown(shard_step)
-        out["breakdown"]["note"] = ("each part timed alone after the timed loop, rank 0 (events); in the step the exchanges "
-                                    "run under the interior launches")
-        if out["breakdown"].get("dw_ms"):
-            flops = 2.0 * shard.n * F * shard_step.Fo
-            tf = flops / (out["breakdown"]["dw_ms"] * 1e-3) / 1e12
-            out["roofline"]["dense"] = {"bound": "mfma", "kernel": "dW = dZ . P^T on rank 0's rows (timed alone after the loop)",
-                                        "achieved": tf, "peak": MFMA_F32_PEAK_TFLOPS, "unit": "TFLOP/s",
-                                        "frac": tf / MFMA_F32_PEAK_TFLOPS, "flops_per_launch": flops,
-                                        "avg_launch_ms": out["breakdown"]["dw_ms"]}
+    elif world > 1:
+        if args.full:
+            with phase("parity of every rank against the oracle", factor=3.0):
+                out["parity"] = parity_sharded(shard_step, shard, seeds, dev) if not shard_step.transform_first else None
+            ok = out["parity"] is None or out["parity"]["ok"]
+            with phase("breakdown (each part timed alone)", factor=2.0):
+                out["breakdown"] = adist.measure_breakdown(shard_step)
+            out["breakdown"]["note"] = ("each part timed alone after the timed loop, rank 0 (events); in the step the exchanges "
+                                        "run under the interior launches")
+            if out["breakdown"].get("dw_ms"):
+                flops = 2.0 * shard.n * F * shard_step.Fo
+                tf = flops / (out["breakdown"]["dw_ms"] * 1e-3) / 1e12
+                out["roofline"]["dense"] = {"bound": "mfma", "kernel": "dW = dZ . P^T on rank 0's rows (timed alone after the loop)",
+                                            "achieved": tf, "peak": MFMA_F32_PEAK_TFLOPS, "unit": "TFLOP/s",
+                                            "frac": tf / MFMA_F32_PEAK_TFLOPS, "flops_per_launch": flops,
+                                            "avg_launch_ms": out["breakdown"]["dw_ms"]}
         # what rank 0's communicator did: the ranks RCCL itself counts (ncclCommCount), its version, bytes to every peer
         out["rccl"] = adist.c_comm_stats()
         out["config"]["control_plane"] = control_plane_note(backend)
@@ -892,7 +926,7 @@ def main():
         err = transport_error(str(info.get("transport", "")), one_device)
         if err:
             out["ok"], out["error"], ok = False, err, False
-    if world == 1:
+    if world == 1 and args.full:
         # "activation = none for the headline; relu epilogue reported separately" -- the same step with the
         # layer's activation: relu in the forward launch's store (athena_mp_kipf_layer_fwd, act = relu), its reverse factor as one
         # elementwise launch in front of dW and the fused pull.  Timed after the headline's loop; never part of `value`.
@@ -927,7 +961,7 @@ def main():
             del Y, dzr
         except Exception as exc:      # reported beside the headline, never instead of it
             out["relu_epilogue"] = {"error": f"{type(exc).__name__}: {exc}"[:200]}
-    if world == 1 and not args.no_secondary and not args.custom and args.config == "c2":
+    if world == 1 and args.full and not args.no_secondary and not args.custom and args.config == "c2":
         # free the headline's tensors first: configs[3] keeps 33 GB of S and configs[4] holds 50 GB in the children
         P = Z = dW = dX = xd = dzd = g = None
         torch.cuda.empty_cache()

@@ -220,7 +220,7 @@ int athena_mp_activation_fwd(int32_t act, int64_t n, const float *z_dev, float *
 int athena_mp_activation_bwd(int32_t act, int64_t n, const float *y_dev, const float *g_dev, float *dz_dev);
 int athena_mp_axpy(int64_t n, float alpha, const float *x_dev, float *y_dev); /* y += alpha x */
 /* dst = src on the device, one 16-byte element per thread in launch order (stream-ordered; 16-byte aligned pointers): the
- * copy form that reaches the HBM's streaming ceiling -- bench.py times it on 1 GiB and prints the rate beside the roofline
+ * copy form that reaches the HBM's streaming ceiling -- bench.py --full times it on 1 GiB and prints the rate beside the roofline
  * as the measured ceiling of the box it ran on (SURVEY.md 8d "report the measured stream ceiling alongside") */
 int athena_mp_device_copy(void *dst_dev, const void *src_dev, uint64_t bytes);
 

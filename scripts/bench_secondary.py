@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The secondary BASELINE configurations as ONE json object each, for bench.py's `secondary` block (N = 1 only):
+"""The secondary BASELINE configurations as ONE json object each, for bench.py's `secondary` block (--full, N = 1 only):
 
     python scripts/bench_secondary.py --config c3     configs[2]: Duvenaud, 130 k QM9-shaped graphs, F_v = 64, F_e = 8
     python scripts/bench_secondary.py --config c4     configs[3]: GNO layer step on a 2 M-point radius mesh, 64 features
@@ -13,7 +13,7 @@ per-op times from HIP events (median of --reps launches after one warm-up), the 
 the bound SURVEY.md 8d names for it (HBM 8 TB/s on algorithmic bytes; fp32 MFMA 157.3 TFLOP/s for the GNO contractions),
 and a parity flag of the SAME device results against the CPU oracle on a sample (block-diagonal batches: the first
 graphs are an exact sub-problem; meshes and the random graph: sampled rows / columns as compact sub-problems).
-bench.py runs this as a CHILD process after its timed loop, so that a failure here is `secondary.error` in the line and
+bench.py --full runs this as a CHILD process after its timed loop, so that a failure here is `secondary.error` in the line and
 never touches the headline value or the exit code.  The oracle is the checker here, never the thing measured."""
 import argparse
 import json

@@ -331,16 +331,16 @@ def test_fortran_processes_run_the_sharded_step_through_the_c_abi(dev, oracle, t
                                        (["--gpus", "4", "--nodes", "200000", "--pairs", "900000"], "p2p"),
                                        (["--gpus", "2", "--config", "c5-local", "--nodes", "400000", "--pairs", "2800000"], "auto")])
 def test_bench_py_multi_gpu_command_dry_run_on_one_device(dev, argv, mode):
-    """`python bench.py --gpus N` -- what the driver launches on an 8-GPU node -- through the one-device dry run
-    (ATHENA_MP_BENCH_ONE_DEVICE=1, gloo process group, comm.hip's host-staged test transport): self-launch, strong-scaling
-    shards of the metric's own graph, both exchanges, parity of every rank against the oracle, the breakdown.  The
-    numbers mean nothing here; the line's structure and its parity do."""
+    """`python bench.py --gpus N --full` -- what the driver launches on an 8-GPU node, with the checks -- through the one-device
+    dry run (ATHENA_MP_BENCH_ONE_DEVICE=1, gloo process group, comm.hip's host-staged test transport): self-launch,
+    strong-scaling shards of the metric's own graph, both exchanges, parity of every rank against the oracle, the breakdown.
+    The numbers mean nothing here; the line's structure and its parity do."""
     import json
     import subprocess
 
     env = dict(os.environ, ATHENA_MP_BENCH_ONE_DEVICE="1", ATHENA_MP_BENCH_BACKEND="gloo", ATHENA_MP_HALO_MODE=mode)
     env.pop("WORLD_SIZE", None); env.pop("RANK", None); env.pop("LOCAL_RANK", None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1"] + argv,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "1"] + argv,
                        env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -857,7 +857,7 @@ def test_bench_py_fails_fast_when_a_rank_stalls(dev, where, phase):
 
 @pytest.mark.parametrize("gpus", [1, 2, 4])
 def test_bench_py_gno_mesh_config(dev, gpus):
-    """`python bench.py --config c4-mesh --gpus N`: graph_nop_layer forward + reverse on the configs[3] mesh generator (here
+    """`python bench.py --config c4-mesh --gpus N --full`: graph_nop_layer forward + reverse on the configs[3] mesh generator (here
     48 000 points) cut by rows -- one rank (empty halo) and the one-device dry run at 2 and 4 ranks (shm test transport);
     the line's structure, the parity of every rank against the materialising oracle, S kept on the blocks."""
     import json
@@ -866,7 +866,7 @@ def test_bench_py_gno_mesh_config(dev, gpus):
     env = dict(os.environ, ATHENA_MP_BENCH_ONE_DEVICE="1", ATHENA_MP_BENCH_BACKEND="gloo")
     env.pop("WORLD_SIZE", None); env.pop("RANK", None); env.pop("LOCAL_RANK", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "c4-mesh", "--gpus", str(gpus), "--nodes", "48000",
-                        "--steps", "2", "--warmup", "1"], env=env, capture_output=True, text=True, timeout=900)
+                        "--steps", "2", "--warmup", "1", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == gpus and line["unit"] == "edges/s" and line["roofline"]["bound"] == "mfma"
@@ -915,8 +915,8 @@ def test_c_abi_transfers_have_a_deadline_of_their_own(dev, tmp_path):
 
 
 def test_bench_line_on_one_gpu_carries_what_the_driver_reads(dev):
-    """`python bench.py` (N = 1, the command the driver issues; here with one CPU run and only configs[2] in the secondary block
-    to keep it short): ONE json line with the contract's fields, `roofline` incl. the copy ceiling measured in the same run,
+    """`python bench.py --full` (N = 1; here with one CPU run and only configs[2] in the secondary block to keep it short):
+    ONE json line with the contract's fields, `roofline` incl. the copy ceiling measured in the same run,
     `cpu_baseline` with its per-run times, `parity.ok`, the relu-epilogue step reported separately, and
     `secondary` as a block of its own whose failure would not touch `value`."""
     import json
@@ -925,7 +925,7 @@ def test_bench_line_on_one_gpu_carries_what_the_driver_reads(dev):
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "ATHENA_MP_BENCH_ONE_DEVICE", "ATHENA_MP_BENCH_BACKEND"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "10", "--warmup", "2", "--cpu-runs", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "10", "--warmup", "2", "--cpu-runs", "1",
                         "--secondary", "c3"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -946,6 +946,39 @@ def test_bench_line_on_one_gpu_carries_what_the_driver_reads(dev):
     sec = d["secondary"]
     assert "error" not in sec and sec["configs[2]"]["parity"]["ok"] and sec["configs[2]"]["step_ms"] > 0
     assert "cpu_baseline" in sec["configs[2]"] and set(sec) >= {"note", "configs[2]", "wall_s"}
+
+
+@pytest.mark.parametrize("argv", [[],                                                         # the headline's own command
+                                  ["--gpus", "2", "--nodes", "200000", "--pairs", "900000"],
+                                  ["--config", "c4-mesh", "--nodes", "48000"],
+                                  ["--config", "c4-mesh", "--gpus", "2", "--nodes", "48000"]])
+def test_plain_bench_line_leaves_the_checks_to_full(dev, argv, tmp_path):
+    """`python bench.py` without --full: set-up, warm-up, the timed steps, --dump-outputs and ONE json line with the contract's
+    fields and the roofline of the timed loop's own events -- no oracle, CPU baseline, copy ceiling, relu epilogue, secondary
+    block or breakdown (N > 1 through the one-device dry run)"""
+    import json
+    import subprocess
+
+    one = "--gpus" not in argv
+    env = dict(os.environ, ATHENA_MP_BENCH_ONE_DEVICE="1", ATHENA_MP_BENCH_BACKEND="gloo")
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK") + (("ATHENA_MP_BENCH_ONE_DEVICE", "ATHENA_MP_BENCH_BACKEND") if one else ()):
+        env.pop(k, None)
+    dump = ["--dump-outputs", str(tmp_path / "out")] if one else []
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1"] + argv + dump,
+                       env=env, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["metric"] == "msgpass fwd+bwd edges/sec" and d["unit"] == "edges/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f32" and d["steps"] == 3 and d["warmup"] == 1 and d["n_gpus"] == (1 if one else 2)
+    assert abs(d["value"] * d["ms_per_step"] * 1e-3 - d["config"]["entries"]) <= 1e-9 * d["config"]["entries"]
+    for k in ("parity", "cpu_baseline", "relu_epilogue", "secondary", "breakdown"):
+        assert k not in d, k
+    assert "measured_copy_ceiling_GBps" not in d["roofline"] and d["roofline"]["avg_launch_ms"] > 0
+    if one:
+        names = ("out", "dX", "dtheta", "dW", "db") if "c4-mesh" in argv else ("P", "Z", "dW", "dX")   # no dcoords: need_coord_grad is off
+        assert all((tmp_path / "out" / (k + ".npy")).exists() for k in names), sorted(os.listdir(tmp_path / "out"))
 
 
 def _directed_worker(rank, world, port, q):

@@ -349,6 +349,23 @@ def test_bench_line_refuses_the_test_transport_outside_the_dry_run():
     assert bench.transport_error("torch.distributed point-to-point (python plan) -- FALLBACK, the C-ABI path failed: x", False)
 
 
+def test_bench_checks_and_extra_measurements_wait_for_full(monkeypatch):
+    """a plain `bench.py --gpus 1 --steps N --warmup W` does only what its headline needs; parity, the CPU baseline, the
+    relu epilogue, the secondary block and the breakdown run with --full, which is off by default"""
+    import importlib.util
+    import sys
+
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    args = bench.parse_args()
+    assert args.full is False and (args.steps, args.warmup, args.gpus) == (7, 2, 1)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--cpu-runs", "1", "--secondary", "c3"])
+    args = bench.parse_args()
+    assert args.full is True and args.cpu_runs == 1 and args.secondary == "c3"
+
+
 def test_watchdog_ends_a_stalled_rank_with_a_message_and_exit_code_3():
     """athena_amd.dist.Watchdog (bench.py's guard around every wait for a peer): a phase that outlives its deadline ends the
     PROCESS -- one json line {"ok": false, "error": "rank r stalled in <phase> ..."} on stdout, exit code 3, no cleanup that
