@@ -310,11 +310,8 @@ static int graph_free(athena_mp_graph *g)
         if (p) (void)hipFree(p);
     if (g->bucket_perm) (void)hipFree(g->bucket_perm);
     if (g->t_entry) (void)hipFree(g->t_entry);
-    for (int32_t *lp : {g->len_perm_fwd, g->len_perm_bwd})
-        if (lp) {
-            amp::gno_forget_perm(lp);
-            (void)hipFree(lp);
-        }
+    if (g->len_fwd.perm) (void)hipFree(g->len_fwd.perm);
+    if (g->len_bwd.perm) (void)hipFree(g->len_bwd.perm);
     if (g->btile_start) (void)hipFree(g->btile_start);
     if (g->btile_info) (void)hipFree(g->btile_info);
     if (g->btile_rows) (void)hipFree(g->btile_rows);

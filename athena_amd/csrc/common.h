@@ -72,6 +72,13 @@ struct LongPlan {
     int32_t *row_task0 = nullptr;                     // [n_long+1] first task of each long row
 };
 
+// rows of a CSR ordered by length, longest first, built on first use by the GNO kernels of gno64.hip: the rows of a tile then
+// have (nearly) equal entry counts, so no wave waits at the tile barrier for a longer row
+struct LenOrder {
+    int32_t *perm = nullptr;      // [rows] device
+    int32_t n_long = 0, n_mid = 0;   // rows with more than 32 / more than 16 entries (n_long included): the first slots of perm
+};
+
 // ---- graph handle: everything the kernels need, resident in HBM --------------------------------
 inline uint64_t next_graph_serial()
 {
@@ -117,12 +124,7 @@ struct athena_mp_graph {
     mutable int bucket_min = 0, bucket_max = -1;
     mutable int32_t *bucket_perm = nullptr;      // [n_rows] device
     mutable std::vector<int64_t> bucket_off;     // [n_buckets+1] host
-    // rows ordered by length (longest first), built on first use by the fused GNO kernel: the 16 rows of a
-    // tile then have (nearly) equal entry counts, so no wave waits at the tile barrier for a longer row
-    mutable int32_t *len_perm_fwd = nullptr;     // [n_rows] device, forward CSR
-    mutable int32_t n_long_fwd = 0;              // rows of the forward CSR with more than 32 entries (the first slots of len_perm_fwd)
-    mutable int32_t n_mid_fwd = 0;               // ... with more than 16 entries (n_long_fwd included)
-    mutable int32_t *len_perm_bwd = nullptr;     // [n_cols] device, transposed CSR
+    mutable LenOrder len_fwd, len_bwd;           // of the forward CSR [n_rows] / the transposed CSR [n_cols]
     // forward entry of every transposed entry (-1: no edge column), built on first use by athena_mp_gno_aggregate_bwd
     mutable int32_t *t_entry = nullptr;          // [nnz] device
     // the same runs cut into 16-vertex tiles (one MFMA column block each), bucket-major
@@ -143,7 +145,6 @@ int graph_build_device(athena_mp_graph *g, const int32_t *adj_ja, const std::vec
 int csr_from_edges_core(int32_t n_vertices, int64_t n_pairs, const int32_t *index_list, int32_t add_self_loops,
                         int32_t *adj_ia_out, int32_t *adj_ja_out, int64_t capacity, int64_t *nnz_out,
                         int32_t **keep_ja_dev);
-void gno_forget_perm(const int32_t *perm_dev);   // gno.hip: counts cached beside a row-length order
 void graph_cache_clear(); // idle and live handles of athena_mp_graph_acquire (capi.hip)
 void host_pool_release();   // staging buffers of the *_host entry points (host.hip)
 uint64_t content_hash(const void *p, size_t bytes);   // every byte of a host array (capi.hip)
@@ -202,4 +203,23 @@ int duv_mfma_bwd_readout(const athena_mp_graph *g, int Fi, int Fo, int O, int ac
                          const float *dz_next, const float *p, const int32_t *tgid, const float *gout, const float *R, float *da,
                          float *da_tail, float *dw, float *dr_slabs, int *n_slabs, bool accumulate_tail,
                          const float *a_tail = nullptr);
+// Graph neural operator at H = F_in = F_out = 64 (gno64.hip): the kernels that keep S / T / G on chip.  gno64_shape is the shape
+// test with the bound on d as its argument (4: gno_fused_kernel, 3: everything that builds buffer descriptors).
+bool gno64_shape(int H, int Fi, int Fo, int d, int d_max);
+// bytes of S the forward pass keeps for the reverse pass; 0: this shape or size does not keep S
+int64_t gno64_saved_bytes(const athena_mp_graph *g, int d, int H, int Fi, int Fo);
+// *ok: the reverse pass runs as ONE call (gno_dh_pc_kernel<.., PX>: dx and dtheta from one G)
+int gno64_one_call_reverse(const athena_mp_graph *g, int d, int H, int Fi, int Fo, bool want_dx, bool *ok);
+// out[r,:] = S_r . Vaug over the n_rows rows of one CSR (gno_pc_kernel; gno_fused_kernel at d = 4 and beyond 4 GB); save: keeps S
+int launch_gno_fused(const int32_t *rowptr, const int32_t *idx, const int32_t *eidx, const float *y, const float *coords,
+                     const float *theta, int d, const float *Vaug, int n_rows, LenOrder *order, float *out, int y_rows,
+                     int n_edge_cols, int64_t nnz, float *save = nullptr);
+// dVaug = S^T g (gno_stg_kernel), S rebuilt or streamed from save; -1: beyond what a buffer descriptor addresses
+int launch_gno_stg(const athena_mp_graph *g, const float *x, const float *coords, const float *theta, int d, const float *grad,
+                   float *dV, const float *save = nullptr);
+// dU, db_u -> dtheta, the masked dh per entry -> ghbuf, the feature gradient's per-entry partials -> px (each may be null)
+int gno64_mlp_backward(const athena_mp_graph *g, int d, const float *theta, const float *coords, const float *x, const float *grad,
+                       float *dtheta, float *ghbuf, float *px, size_t px_half, const float *cvec);
+int gno64_t_entry(const athena_mp_graph *g);   // g->t_entry, built once; -1: the device cannot hold it
+int gno64_px_gather(const athena_mp_graph *g, const float *px, float *dx, hipStream_t s);   // dx from the partials, on stream s
 } // namespace amp

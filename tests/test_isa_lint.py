@@ -78,14 +78,14 @@ def test_lint_goes_red_when_by_group_is_reverted(tmp_path):
     """Round 4's accident, replayed: GnoProd::by_group written as the indexed read a[g] makes the compiler park the array in
     scratch and read it back with a per-lane index inside the tile loop (5.8 GB per launch at configs[3],
     profiles/r04_c4_scratch_ab.txt).  The lint must see it in gno_pc_kernel."""
-    src = open(os.path.join(ROOT, "athena_amd", "csrc", "gno.hip")).read()
+    src = open(os.path.join(ROOT, "athena_amd", "csrc", "gno64.hip")).read()
     a = src.index("    __device__ __forceinline__ int by_group(const int (&a)[4]) const")
     b = src.index("    __device__ __forceinline__ void ids_entries(GnoIds &I) const")
     reverted = src[:a] + "    __device__ __forceinline__ int by_group(const int (&a)[4]) const { return a[g]; }\n" + src[b:]
-    (tmp_path / "gno.hip").write_text(reverted)
+    (tmp_path / "gno64.hip").write_text(reverted)
     lib = tmp_path / "libgno_reverted.so"
     subprocess.check_call([HIPCC, *FLAGS, "-I", os.path.join(ROOT, "athena_amd", "csrc"), "-I", os.path.join(ROOT, "include"),
-                           "-shared", str(tmp_path / "gno.hip"), "-o", str(lib)], stderr=subprocess.DEVNULL)
+                           "-shared", str(tmp_path / "gno64.hip"), "-o", str(lib)], stderr=subprocess.DEVNULL)
     rows = isa_lint.analyse(str(lib))
     v = isa_lint.violations(rows, require_exact=False)
     assert any(x.startswith("R1 gno_pc_kernel<false>") for x in v), v
