@@ -383,15 +383,15 @@ int athena_mp_graph_create(int32_t n_rows, int32_t n_cols, int64_t nnz, const in
 /* edge list -> CSR -> handle without the entries leaving HBM in between (graphstruc's generate_adjacency
  * [+ add_self_loops] followed by set_graph).  adj_ia_out (n_vertices + 1, host) is always filled; adj_ja_out
  * (2 x capacity, host) only when non-null -- a caller that keeps the graph_type needs it, the layers do not. */
-int athena_mp_graph_create_from_edges(int32_t n_vertices, int64_t n_pairs, const int32_t *index_list,
-                                      int32_t add_self_loops, int32_t with_edge_ids, int32_t *adj_ia_out,
-                                      int32_t *adj_ja_out, int64_t capacity, int64_t *nnz_out, athena_mp_graph **out)
+static int graph_from_edges_impl(int32_t n_vertices, int64_t n_pairs, const int32_t *index_list, bool list_on_device,
+                                 int32_t add_self_loops, int32_t with_edge_ids, int32_t *adj_ia_out, int32_t *adj_ja_out,
+                                 int64_t capacity, int64_t *nnz_out, athena_mp_graph **out)
 {
     AMP_REQUIRE(out != nullptr && nnz_out != nullptr && adj_ia_out != nullptr, "graph_create_from_edges: null output pointer");
     *out = nullptr;
     int32_t *ja_dev = nullptr;
     int rc = amp::csr_from_edges_core(n_vertices, n_pairs, index_list, add_self_loops, adj_ia_out, adj_ja_out, capacity,
-                                      nnz_out, &ja_dev);
+                                      nnz_out, &ja_dev, list_on_device);
     if (rc) {
         if (ja_dev) (void)hipFree(ja_dev);
         return rc;
@@ -404,6 +404,23 @@ int athena_mp_graph_create_from_edges(int32_t n_vertices, int64_t n_pairs, const
                            ja_dev, n_edge_cols, nullptr, nullptr, out);
     (void)hipFree(ja_dev);
     return rc;
+}
+
+int athena_mp_graph_create_from_edges(int32_t n_vertices, int64_t n_pairs, const int32_t *index_list,
+                                      int32_t add_self_loops, int32_t with_edge_ids, int32_t *adj_ia_out,
+                                      int32_t *adj_ja_out, int64_t capacity, int64_t *nnz_out, athena_mp_graph **out)
+{
+    return graph_from_edges_impl(n_vertices, n_pairs, index_list, false, add_self_loops, with_edge_ids, adj_ia_out, adj_ja_out,
+                                 capacity, nnz_out, out);
+}
+
+/* the same for an index list that is already in HBM (the pair list of athena_mp_radius_pairs): nothing is uploaded */
+int athena_mp_graph_create_from_edges_dev(int32_t n_vertices, int64_t n_pairs, const int32_t *index_list_dev,
+                                          int32_t add_self_loops, int32_t with_edge_ids, int32_t *adj_ia_out,
+                                          int32_t *adj_ja_out, int64_t capacity, int64_t *nnz_out, athena_mp_graph **out)
+{
+    return graph_from_edges_impl(n_vertices, n_pairs, index_list_dev, true, add_self_loops, with_edge_ids, adj_ia_out, adj_ja_out,
+                                 capacity, nnz_out, out);
 }
 
 static int graph_create_body(int32_t n_rows, int32_t n_cols, int64_t nnz, const int32_t *adj_ia,

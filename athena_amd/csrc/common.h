@@ -59,6 +59,21 @@ struct PerDeviceFlag {
     bool &get() { return done[device()]; }
 };
 
+// device scratch of one call: every array handed out is returned to the device on every exit path
+struct Scratch {
+    std::vector<void *> ptrs;
+    template <typename T> int get(T **p, size_t count)
+    {
+        AMP_HIP(hipMalloc((void **)p, sizeof(T) * (count ? count : 1)));
+        ptrs.push_back(*p);
+        return 0;
+    }
+    ~Scratch()
+    {
+        for (void *p : ptrs) (void)hipFree(p);
+    }
+};
+
 } // namespace amp
 
 // Rows longer than kLongRow entries (hubs of heavy-tailed graphs) are cut into segments of kLongRow
@@ -144,7 +159,7 @@ int graph_build_device(athena_mp_graph *g, const int32_t *adj_ja, const std::vec
                        std::vector<int32_t> *t_rowptr_host, const int32_t *adj_ja_dev = nullptr);
 int csr_from_edges_core(int32_t n_vertices, int64_t n_pairs, const int32_t *index_list, int32_t add_self_loops,
                         int32_t *adj_ia_out, int32_t *adj_ja_out, int64_t capacity, int64_t *nnz_out,
-                        int32_t **keep_ja_dev);
+                        int32_t **keep_ja_dev, bool list_on_device = false);
 void graph_cache_clear(); // idle and live handles of athena_mp_graph_acquire (capi.hip)
 void host_pool_release();   // staging buffers of the *_host entry points (host.hip)
 uint64_t content_hash(const void *p, size_t bytes);   // every byte of a host array (capi.hip)

@@ -114,19 +114,7 @@ template <typename T> int dev_alloc(T **p, size_t count)
     return 0;
 }
 
-struct Scratch {   // freed on every exit path
-    std::vector<void *> ptrs;
-    template <typename T> int get(T **p, size_t count)
-    {
-        if (dev_alloc(p, count)) return 1;
-        ptrs.push_back(*p);
-        return 0;
-    }
-    ~Scratch()
-    {
-        for (void *p : ptrs) (void)hipFree(p);
-    }
-};
+using amp::Scratch;
 
 } // namespace
 
@@ -358,10 +346,11 @@ __global__ void csr_entries_kernel(int64_t nnz, const unsigned long long *__rest
 
 namespace amp {
 // the edge list -> CSR pass.  adj_ja_out: host copy of the entries (may be null); keep_ja_dev: when non-null the
-// device copy of the entries is handed to the caller (hipFree it) instead of being released
+// device copy of the entries is handed to the caller (hipFree it) instead of being released; list_on_device: index_list
+// is already in HBM (a pair list athena_mp_radius_pairs wrote) and is read in place
 int csr_from_edges_core(int32_t n_vertices, int64_t n_pairs, const int32_t *index_list, int32_t add_self_loops,
                         int32_t *adj_ia_out, int32_t *adj_ja_out, int64_t capacity, int64_t *nnz_out,
-                        int32_t **keep_ja_dev)
+                        int32_t **keep_ja_dev, bool list_on_device)
 {
     AMP_REQUIRE(n_vertices >= 0 && n_pairs >= 0 && nnz_out && adj_ia_out && (n_pairs == 0 || index_list),
                 "csr_from_edges: bad arguments");
@@ -372,7 +361,7 @@ int csr_from_edges_core(int32_t n_vertices, int64_t n_pairs, const int32_t *inde
     Scratch tmp;
     int32_t *d_pairs = nullptr, *d_dst = nullptr, *d_dst_s = nullptr, *d_dst_t = nullptr, *d_loop = nullptr, *d_ia = nullptr, *d_ja = nullptr;
     unsigned long long *d_keys = nullptr, *d_keys_s = nullptr, *d_keys_t = nullptr, *d_bad = nullptr;
-    if (tmp.get(&d_pairs, 2 * (size_t)n_pairs) || tmp.get(&d_dst, total) || tmp.get(&d_dst_s, total) || tmp.get(&d_dst_t, total) ||
+    if ((!list_on_device && tmp.get(&d_pairs, 2 * (size_t)n_pairs)) || tmp.get(&d_dst, total) || tmp.get(&d_dst_s, total) || tmp.get(&d_dst_t, total) ||
         tmp.get(&d_loop, n_vertices) || tmp.get(&d_ia, (size_t)n_vertices + 1) || tmp.get(&d_keys, total) ||
         tmp.get(&d_keys_s, total) || tmp.get(&d_keys_t, total) || tmp.get(&d_bad, 1))
         return 1;
@@ -380,7 +369,10 @@ int csr_from_edges_core(int32_t n_vertices, int64_t n_pairs, const int32_t *inde
     AMP_HIP(hipMemcpyAsync(d_bad, &none, sizeof(none), hipMemcpyHostToDevice, st));
     AMP_HIP(hipMemsetAsync(d_loop, 0, sizeof(int32_t) * (size_t)std::max(n_vertices, 1), st));
     if (n_pairs > 0) {
-        AMP_HIP(hipMemcpyAsync(d_pairs, index_list, sizeof(int32_t) * 2 * (size_t)n_pairs, hipMemcpyHostToDevice, st));
+        if (list_on_device)
+            d_pairs = const_cast<int32_t *>(index_list);
+        else
+            AMP_HIP(hipMemcpyAsync(d_pairs, index_list, sizeof(int32_t) * 2 * (size_t)n_pairs, hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(edge_entries_kernel, dim3(blocks(n_pairs)), dim3(256), 0, st, n_pairs, (const int32_t *)d_pairs,
                            n_vertices, stride, d_keys, d_dst, d_loop, d_bad);
         AMP_LAUNCH_CHECK();
@@ -394,8 +386,9 @@ int csr_from_edges_core(int32_t n_vertices, int64_t n_pairs, const int32_t *inde
     AMP_HIP(hipMemcpyAsync(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost, st));
     AMP_HIP(hipStreamSynchronize(st));
     if (bad != none) {
-        set_error("csr_from_edges: index_list(:,%llu) = (%d, %d) outside [1,%d]", bad + 1, index_list[2 * bad],
-                  index_list[2 * bad + 1], n_vertices);
+        int32_t pair[2] = {0, 0};   // read back: the list may live on either side
+        AMP_HIP(hipMemcpy(pair, d_pairs + 2 * bad, sizeof(pair), hipMemcpyDeviceToHost));
+        set_error("csr_from_edges: index_list(:,%llu) = (%d, %d) outside [1,%d]", bad + 1, pair[0], pair[1], n_vertices);
         return 2;
     }
     int64_t nnz = 0;
@@ -445,5 +438,5 @@ extern "C" int athena_mp_csr_from_edges(int32_t n_vertices, int64_t n_pairs, con
                                         int64_t capacity, int64_t *nnz_out)
 {
     return amp::csr_from_edges_core(n_vertices, n_pairs, index_list, add_self_loops, adj_ia_out, adj_ja_out, capacity,
-                                    nnz_out, nullptr);
+                                    nnz_out, nullptr, false);
 }

@@ -1,0 +1,489 @@
+// Points -> radius graph on the device: the step in front of athena_mp_csr_from_edges / athena_mp_graph_create_from_edges for
+// graph_nop_layer_type's inputs (a radius graph of a point cloud and its edge geometry, athena_graph_nop_layer.f90:743-758).
+// graphstruc has no such call.
+//
+// The definition (every implementation gives the same arrays; tests compare with np.array_equal):
+//   * delta = p_i - p_j component by component in fp32, s = ((d0*d0) + d1*d1) + d2*d2 with every multiply and add rounded to
+//     fp32 on its own (the library is built with -ffp-contract=off); i < j are joined iff s <= fl(radius * radius).  No self
+//     pairs; two points at the same place are joined.
+//   * pairs are numbered in lexicographic order of (i, j), i < j; coords[e, :] = p_i - p_j (smaller index minus larger).
+//
+// How: a uniform grid whose cells are at least radius * (1 + 2^-10) wide on every axis, at most kMaxCellsAxis cells per axis and
+// at most 2 n cells in all; a stable radix sort of (cell, point id) (radix_sort.h), the positions copied into cell order; a COUNT
+// pass in which every point counts its partners with a larger id in the 3^dim cells around it; an exclusive scan of the counts
+// IN POINT-ID ORDER (64-bit offsets), so the rows of the pair list already sit in lexicographic order of i; a FILL pass that
+// writes the keys i * n + j into those rows; one radix sort of the keys, which puts the partners of every row in ascending
+// order; one pass that decodes the keys into the 1-based pair list and the coordinate differences.  No atomics on data: counts,
+// offsets and the final order are functions of the input alone.
+//
+// Why the margin: the cell of a coordinate is floor(fl(fl(p - lo) * inv_w)) clamped to the axis -- monotone in p, each of the two
+// roundings within 2^-24 relative, so a computed cell coordinate q is within 3 * 2^-24 * q <= 3 * 2^-24 * kMaxCellsAxis of the
+// exact one.  A pair the predicate keeps has |p_i - p_j| <= radius * (1 + 2^-22) on every axis, i.e. at most
+// (1 + 2^-22) / (1 + 2^-10) < 1 - 2^-10 + 2^-19 cells apart exactly, and 6 * 2^-24 * 2048 + 2^-19 < 2^-10: the computed
+// coordinates differ by less than one, the cells by at most one.
+#include <math.h>
+
+#include <algorithm>
+
+#include "common.h"
+#include "radix_sort.h"
+
+namespace {
+
+constexpr int kMaxCellsAxis = 2048;
+constexpr double kCellMargin = 1.0 / 1024.0;
+constexpr int kBoxBlocks = 512;
+
+struct Box {
+    float lo[3], hi[3];
+    unsigned long long first_bad;   // smallest index of a point with a non-finite coordinate, ~0 if none
+};
+
+struct Grid {
+    float lo[3], inv_w[3];
+    int32_t nc[3];
+};
+
+// ---- bounding box + validity: block partials, then one block folds them in block order -------------------------------------
+__device__ inline void box_fold(Box &a, const Box &b)
+{
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        a.lo[k] = fminf(a.lo[k], b.lo[k]);
+        a.hi[k] = fmaxf(a.hi[k], b.hi[k]);
+    }
+    a.first_bad = b.first_bad < a.first_bad ? b.first_bad : a.first_bad;
+}
+
+__device__ inline Box box_block_reduce(Box b)
+{
+    __shared__ Box part[256];
+    part[threadIdx.x] = b;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) box_fold(part[threadIdx.x], part[threadIdx.x + s]);
+        __syncthreads();
+    }
+    return part[0];
+}
+
+__device__ inline Box box_empty()
+{
+    Box b;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        b.lo[k] = INFINITY;
+        b.hi[k] = -INFINITY;
+    }
+    b.first_bad = ~0ull;
+    return b;
+}
+
+__global__ __launch_bounds__(256) void rg_box_kernel(int32_t n, int dim, const float *__restrict__ pts, Box *__restrict__ partial)
+{
+    Box b = box_empty();
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        bool ok = true;
+        for (int k = 0; k < dim; ++k) {
+            const float v = pts[i * dim + k];
+            ok = ok && isfinite(v);
+            b.lo[k] = fminf(b.lo[k], v);
+            b.hi[k] = fmaxf(b.hi[k], v);
+        }
+        if (!ok && (unsigned long long)i < b.first_bad) b.first_bad = (unsigned long long)i;
+    }
+    b = box_block_reduce(b);
+    if (threadIdx.x == 0) partial[blockIdx.x] = b;
+}
+
+__global__ __launch_bounds__(256) void rg_box_final_kernel(int n_partial, const Box *__restrict__ partial, Box *__restrict__ out)
+{
+    Box b = box_empty();
+    for (int i = threadIdx.x; i < n_partial; i += 256) box_fold(b, partial[i]);
+    b = box_block_reduce(b);
+    if (threadIdx.x == 0) *out = b;
+}
+
+// ---- grid ------------------------------------------------------------------------------------------------------------------
+__device__ inline int32_t cell_coord(float p, float lo, float inv_w, int32_t nc)
+{
+    const float q = (p - lo) * inv_w;
+    const int32_t c = (int32_t)q;             // q >= 0 and finite: truncation is floor
+    return c < nc - 1 ? c : nc - 1;
+}
+
+__global__ __launch_bounds__(256) void rg_cell_key_kernel(int32_t n, int dim, const float *__restrict__ pts, Grid g,
+                                                          uint32_t *__restrict__ key)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    uint32_t c = 0;
+    for (int k = dim - 1; k >= 0; --k) c = c * (uint32_t)g.nc[k] + (uint32_t)cell_coord(pts[i * dim + k], g.lo[k], g.inv_w[k], g.nc[k]);
+    key[i] = c;
+}
+
+// positions in cell order: a cell's points are one contiguous read
+__global__ __launch_bounds__(256) void rg_gather_points_kernel(int32_t n, int dim, const float *__restrict__ pts,
+                                                               const int32_t *__restrict__ perm, float *__restrict__ sorted)
+{
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k >= n) return;
+    const int64_t i = perm[k];
+    for (int a = 0; a < dim; ++a) sorted[k * dim + a] = pts[i * dim + a];
+}
+
+// cell_start[c] = first slot whose sorted key is >= c  (c = 0 .. n_cells)
+__global__ __launch_bounds__(256) void rg_cell_start_kernel(uint32_t n_cells, const uint32_t *__restrict__ sorted_key, int32_t n,
+                                                            int32_t *__restrict__ cell_start)
+{
+    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (c > (int64_t)n_cells) return;
+    int32_t lo = 0, hi = n;
+    while (lo < hi) {
+        const int32_t mid = lo + ((hi - lo) >> 1);
+        if ((int64_t)sorted_key[mid] < c) lo = mid + 1; else hi = mid;
+    }
+    cell_start[c] = lo;
+}
+
+// ---- the predicate, term by term in fp32 (-ffp-contract=off: no fused multiply-add) --------------------------------------------
+template <int DIM> __device__ inline bool joined(const float *__restrict__ a, const float *__restrict__ b, float r2)
+{
+    const float d0 = a[0] - b[0];
+    float s = d0 * d0;
+    if (DIM > 1) {
+        const float d1 = a[1] - b[1];
+        s = s + d1 * d1;
+    }
+    if (DIM > 2) {
+        const float d2 = a[2] - b[2];
+        s = s + d2 * d2;
+    }
+    return s <= r2;
+}
+
+// One thread per slot of the cell order: the point i = perm[slot] against every point j > i of the 3^DIM cells around its own.
+// FILL = false: count[i] = number of partners.  FILL = true: key[offset[i] + t] = i * n + j for the t-th partner found.
+template <int DIM, bool FILL>
+__global__ __launch_bounds__(256) void rg_neighbour_kernel(int32_t n, Grid g, float r2, const float *__restrict__ sorted,
+                                                           const int32_t *__restrict__ perm, const uint32_t *__restrict__ sorted_key,
+                                                           const int32_t *__restrict__ cell_start, uint32_t *__restrict__ count,
+                                                           const unsigned long long *__restrict__ offset,
+                                                           unsigned long long *__restrict__ key)
+{
+    const int64_t slot = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (slot >= n) return;
+    const int32_t i = perm[slot];
+    float p[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+    for (int a = 0; a < DIM; ++a) p[a] = sorted[slot * DIM + a];
+    uint32_t c = sorted_key[slot];
+    int32_t cc[3] = {0, 0, 0};
+#pragma unroll
+    for (int a = 0; a < DIM; ++a) {
+        cc[a] = (int32_t)(c % (uint32_t)g.nc[a]);
+        c /= (uint32_t)g.nc[a];
+    }
+    uint32_t found = 0;
+    unsigned long long at = 0;
+    if (FILL) at = offset[i];
+    const int z0 = DIM > 2 ? max(cc[2] - 1, 0) : 0, z1 = DIM > 2 ? min(cc[2] + 1, g.nc[2] - 1) : 0;
+    const int y0 = DIM > 1 ? max(cc[1] - 1, 0) : 0, y1 = DIM > 1 ? min(cc[1] + 1, g.nc[1] - 1) : 0;
+    const int x0 = max(cc[0] - 1, 0), x1 = min(cc[0] + 1, g.nc[0] - 1);
+    for (int z = z0; z <= z1; ++z)
+        for (int y = y0; y <= y1; ++y) {
+            // the cells x0 .. x1 of one grid row are consecutive keys: one contiguous run of slots
+            const uint32_t row = (DIM > 2 ? (uint32_t)z * (uint32_t)g.nc[1] : 0u) + (uint32_t)y;
+            const uint32_t first = row * (uint32_t)g.nc[0] + (uint32_t)x0;
+            const int32_t beg = cell_start[first], end = cell_start[first + (uint32_t)(x1 - x0) + 1u];
+            for (int32_t m = beg; m < end; ++m) {
+                const int32_t j = perm[m];
+                if (j <= i) continue;
+                if (!joined<DIM>(p, sorted + (int64_t)m * DIM, r2)) continue;       // p_i - p_j, i < j
+                if (FILL) key[at + found] = (unsigned long long)i * (unsigned long long)n + (unsigned long long)j;
+                ++found;
+            }
+        }
+    if (!FILL) count[i] = found;
+}
+
+// ---- exclusive scan of the counts in point-id order, 64-bit offsets ----------------------------------------------------------
+constexpr int kScanPer = 16;
+constexpr int kScanTile = 256 * kScanPer;
+
+__device__ inline unsigned long long block_scan64(unsigned long long v, unsigned long long *total)
+{
+    __shared__ unsigned long long wsum[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned long long inc = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const unsigned long long up = __shfl_up(inc, d, 64);
+        if (lane >= d) inc += up;
+    }
+    if (lane == 63) wsum[wave] = inc;
+    __syncthreads();
+    unsigned long long off = 0, all = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        if (w < wave) off += wsum[w];
+        all += wsum[w];
+    }
+    __syncthreads();
+    *total = all;
+    return off + inc - v;
+}
+
+__global__ __launch_bounds__(256) void rg_tile_sum_kernel(int32_t n, const uint32_t *__restrict__ count,
+                                                          unsigned long long *__restrict__ tile_sum)
+{
+    const int64_t base = (int64_t)blockIdx.x * kScanTile + (int64_t)threadIdx.x * kScanPer;
+    unsigned long long s = 0;
+    for (int k = 0; k < kScanPer; ++k)
+        if (base + k < n) s += count[base + k];
+    unsigned long long total;
+    (void)block_scan64(s, &total);
+    if (threadIdx.x == 0) tile_sum[blockIdx.x] = total;
+}
+
+// one block: tile_sum becomes the tiles' exclusive offsets, tile_sum[tiles] the grand total
+__global__ __launch_bounds__(256) void rg_scan_tiles_kernel(uint32_t tiles, unsigned long long *__restrict__ tile_sum)
+{
+    unsigned long long carry = 0;
+    for (uint32_t base = 0; base < tiles; base += 256) {
+        const uint32_t t = base + threadIdx.x;
+        const unsigned long long v = t < tiles ? tile_sum[t] : 0ull;
+        unsigned long long total;
+        const unsigned long long ex = block_scan64(v, &total);
+        if (t < tiles) tile_sum[t] = carry + ex;
+        carry += total;
+    }
+    if (threadIdx.x == 0) tile_sum[tiles] = carry;
+}
+
+__global__ __launch_bounds__(256) void rg_scan_apply_kernel(int32_t n, const uint32_t *__restrict__ count,
+                                                            const unsigned long long *__restrict__ tile_off,
+                                                            unsigned long long *__restrict__ offset)
+{
+    const int64_t base = (int64_t)blockIdx.x * kScanTile + (int64_t)threadIdx.x * kScanPer;
+    uint32_t c[kScanPer];
+    unsigned long long s = 0;
+#pragma unroll
+    for (int k = 0; k < kScanPer; ++k) {
+        c[k] = base + k < n ? count[base + k] : 0u;
+        s += c[k];
+    }
+    unsigned long long total;
+    unsigned long long run = tile_off[blockIdx.x] + block_scan64(s, &total);
+#pragma unroll
+    for (int k = 0; k < kScanPer; ++k) {
+        if (base + k < n) offset[base + k] = run;
+        run += c[k];
+    }
+}
+
+// ---- sorted keys -> 1-based pair list [2, E] column-major and coords [E, dim] -------------------------------------------------
+__global__ __launch_bounds__(256) void rg_emit_kernel(int64_t E, int32_t n, int dim, const unsigned long long *__restrict__ key,
+                                                      const float *__restrict__ pts, int32_t *__restrict__ pairs,
+                                                      float *__restrict__ coords)
+{
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= E) return;
+    const unsigned long long k = key[e];
+    const int64_t i = (int64_t)(k / (unsigned long long)n), j = (int64_t)(k % (unsigned long long)n);
+    if (pairs) {
+        pairs[2 * e] = (int32_t)i + 1;
+        pairs[2 * e + 1] = (int32_t)j + 1;
+    }
+    if (coords)
+        for (int a = 0; a < dim; ++a) coords[e * dim + a] = pts[i * dim + a] - pts[j * dim + a];
+}
+
+inline unsigned blocks(int64_t n) { return (unsigned)((n + 255) / 256); }
+inline int bits_for(unsigned long long max_value)
+{
+    int b = 1;
+    while (b < 64 && (max_value >> b)) ++b;
+    return b;
+}
+
+using amp::Scratch;
+
+template <bool FILL, typename... A> void launch_neighbour(int dim, int32_t n, hipStream_t st, A... a)
+{
+    if (dim == 1) hipLaunchKernelGGL((rg_neighbour_kernel<1, FILL>), dim3(blocks(n)), dim3(256), 0, st, n, a...);
+    else if (dim == 2) hipLaunchKernelGGL((rg_neighbour_kernel<2, FILL>), dim3(blocks(n)), dim3(256), 0, st, n, a...);
+    else hipLaunchKernelGGL((rg_neighbour_kernel<3, FILL>), dim3(blocks(n)), dim3(256), 0, st, n, a...);
+}
+
+// at most kMaxCellsAxis cells per axis and 2 n in all, every cell at least radius * (1 + kCellMargin) wide; an axis whose extent
+// is below that is one cell
+Grid make_grid(const Box &box, int dim, int32_t n, float radius)
+{
+    Grid g;
+    double extent[3] = {0, 0, 0};
+    const double h = (double)radius * (1.0 + kCellMargin);
+    for (int a = 0; a < 3; ++a) {
+        g.lo[a] = a < dim ? box.lo[a] : 0.f;
+        g.nc[a] = 1;
+        if (a < dim) {
+            extent[a] = (double)box.hi[a] - (double)box.lo[a];
+            const double cells = floor(extent[a] / h);
+            g.nc[a] = cells < 1.0 ? 1 : cells > (double)kMaxCellsAxis ? kMaxCellsAxis : (int32_t)cells;
+        }
+    }
+    const int64_t cap = std::min<int64_t>(2 * (int64_t)n, (int64_t)1 << 30);
+    while ((int64_t)g.nc[0] * g.nc[1] * g.nc[2] > cap) {
+        int a = 0;
+        for (int k = 1; k < 3; ++k)
+            if (g.nc[k] > g.nc[a]) a = k;
+        g.nc[a] = (g.nc[a] + 1) / 2;
+    }
+    for (int a = 0; a < 3; ++a) g.inv_w[a] = g.nc[a] > 1 ? (float)((double)g.nc[a] / extent[a]) : 0.f;
+    return g;
+}
+
+} // namespace
+
+namespace amp {
+
+// pairs_dev / coords_dev both null: count only.  Everything on the library's stream; synchronised on return.
+int radius_pairs_core(int32_t n, int32_t dim, const float *points_dev, float radius, int32_t *pairs_dev, float *coords_dev,
+                      int64_t capacity, int64_t *n_pairs_out)
+{
+    AMP_REQUIRE(n_pairs_out != nullptr, "radius_pairs: null n_pairs_out");
+    *n_pairs_out = 0;
+    AMP_REQUIRE(dim >= 1 && dim <= 3, "radius_pairs: dim = %d outside [1,3]", dim);
+    AMP_REQUIRE(isfinite(radius) && radius > 0.f, "radius_pairs: radius = %g is not a positive finite number", (double)radius);
+    AMP_REQUIRE(n >= 0 && (n == 0 || points_dev != nullptr), "radius_pairs: bad arguments");
+    if (n == 0) return 0;
+    const float r2 = radius * radius;
+    AMP_REQUIRE(isfinite(r2), "radius_pairs: radius = %g squared is not finite in fp32", (double)radius);
+    hipStream_t st = stream();
+    const bool fill = pairs_dev != nullptr || coords_dev != nullptr;
+
+    Scratch tmp;
+    Box *d_partial = nullptr, *d_box = nullptr;
+    const int box_blocks = (int)std::min<int64_t>(kBoxBlocks, blocks(n));
+    if (tmp.get(&d_partial, box_blocks) || tmp.get(&d_box, 1)) return 1;
+    hipLaunchKernelGGL(rg_box_kernel, dim3(box_blocks), dim3(256), 0, st, n, (int)dim, points_dev, d_partial);
+    hipLaunchKernelGGL(rg_box_final_kernel, dim3(1), dim3(256), 0, st, box_blocks, (const Box *)d_partial, d_box);
+    AMP_LAUNCH_CHECK();
+    Box box;
+    AMP_HIP(hipMemcpyAsync(&box, d_box, sizeof(box), hipMemcpyDeviceToHost, st));
+    AMP_HIP(hipStreamSynchronize(st));
+    if (box.first_bad != ~0ull) {
+        float p[3] = {0.f, 0.f, 0.f};
+        AMP_HIP(hipMemcpy(p, points_dev + box.first_bad * (unsigned long long)dim, sizeof(float) * dim, hipMemcpyDeviceToHost));
+        int a = 0;
+        while (a < dim - 1 && isfinite(p[a])) ++a;
+        set_error("radius_pairs: points(%d,%llu) = %g is not finite", a + 1, box.first_bad + 1, (double)p[a]);
+        return 2;
+    }
+    const Grid grid = make_grid(box, dim, n, radius);
+    const uint32_t n_cells = (uint32_t)((int64_t)grid.nc[0] * grid.nc[1] * grid.nc[2]);
+
+    uint32_t *d_key = nullptr, *d_key_s = nullptr, *d_key_t = nullptr, *d_count = nullptr;
+    int32_t *d_perm = nullptr, *d_perm_t = nullptr, *d_cell_start = nullptr;
+    float *d_sorted = nullptr;
+    unsigned long long *d_tile = nullptr, *d_offset = nullptr;
+    void *d_temp = nullptr;
+    const uint32_t tiles = (uint32_t)(((int64_t)n + kScanTile - 1) / kScanTile);
+    if (tmp.get(&d_key, n) || tmp.get(&d_key_s, n) || tmp.get(&d_key_t, n) || tmp.get(&d_perm, n) || tmp.get(&d_perm_t, n) ||
+        tmp.get(&d_cell_start, (size_t)n_cells + 1) || tmp.get(&d_sorted, (size_t)n * dim) || tmp.get(&d_count, n) ||
+        tmp.get(&d_tile, (size_t)tiles + 1) || tmp.get((char **)&d_temp, radix::scratch_bytes(n)))
+        return 1;
+    hipLaunchKernelGGL(rg_cell_key_kernel, dim3(blocks(n)), dim3(256), 0, st, n, (int)dim, points_dev, grid, d_key);
+    AMP_LAUNCH_CHECK();
+    if (int rc = radix::sort_pairs<uint32_t>((const uint32_t *)d_key, nullptr, n, bits_for(n_cells - 1), d_key_s, d_perm, d_key_t, d_perm_t,
+                                             d_temp, st))
+        return rc;
+    hipLaunchKernelGGL(rg_gather_points_kernel, dim3(blocks(n)), dim3(256), 0, st, n, (int)dim, points_dev, (const int32_t *)d_perm,
+                       d_sorted);
+    hipLaunchKernelGGL(rg_cell_start_kernel, dim3(blocks((int64_t)n_cells + 1)), dim3(256), 0, st, n_cells, (const uint32_t *)d_key_s, n,
+                       d_cell_start);
+    launch_neighbour<false>(dim, n, st, grid, r2, (const float *)d_sorted, (const int32_t *)d_perm, (const uint32_t *)d_key_s,
+                            (const int32_t *)d_cell_start, d_count, (const unsigned long long *)nullptr, (unsigned long long *)nullptr);
+    hipLaunchKernelGGL(rg_tile_sum_kernel, dim3(tiles), dim3(256), 0, st, n, (const uint32_t *)d_count, d_tile);
+    hipLaunchKernelGGL(rg_scan_tiles_kernel, dim3(1), dim3(256), 0, st, tiles, d_tile);
+    AMP_LAUNCH_CHECK();
+    unsigned long long total = 0;
+    AMP_HIP(hipMemcpyAsync(&total, d_tile + tiles, sizeof(total), hipMemcpyDeviceToHost, st));
+    AMP_HIP(hipStreamSynchronize(st));
+    // the limit of csr_from_edges_core, found by the count pass before anything of that size is allocated
+    AMP_REQUIRE(total < (1ull << 31) && 2 * (int64_t)total + n < (int64_t)INT32_MAX,
+                "radius_pairs: %llu pairs among %d points: more than 2^31 CSR entries", total, n);
+    *n_pairs_out = (int64_t)total;
+    if (!fill) return 0;
+    AMP_REQUIRE(capacity >= (int64_t)total, "radius_pairs: the output buffers hold %lld pairs, the graph has %lld", (long long)capacity,
+                (long long)total);
+    if (total == 0) return 0;
+
+    const int64_t E = (int64_t)total;
+    unsigned long long *d_pk = nullptr, *d_pk_s = nullptr, *d_pk_t = nullptr;
+    int32_t *d_v = nullptr, *d_v_t = nullptr;
+    void *d_temp2 = nullptr;
+    if (tmp.get(&d_offset, n) || tmp.get(&d_pk, E) || tmp.get(&d_pk_s, E) || tmp.get(&d_pk_t, E) || tmp.get(&d_v, E) || tmp.get(&d_v_t, E) ||
+        tmp.get((char **)&d_temp2, radix::scratch_bytes(E)))
+        return 1;
+    hipLaunchKernelGGL(rg_scan_apply_kernel, dim3(tiles), dim3(256), 0, st, n, (const uint32_t *)d_count,
+                       (const unsigned long long *)d_tile, d_offset);
+    launch_neighbour<true>(dim, n, st, grid, r2, (const float *)d_sorted, (const int32_t *)d_perm, (const uint32_t *)d_key_s,
+                           (const int32_t *)d_cell_start, (uint32_t *)nullptr, (const unsigned long long *)d_offset, d_pk);
+    AMP_LAUNCH_CHECK();
+    // rows are already in order of i; the sort of the whole key orders the partners inside every row
+    const int key_bits = bits_for((unsigned long long)n * (unsigned long long)n - 1ull);
+    if (int rc = radix::sort_pairs<unsigned long long>((const unsigned long long *)d_pk, nullptr, E, key_bits, d_pk_s, d_v, d_pk_t, d_v_t,
+                                                       d_temp2, st))
+        return rc;
+    hipLaunchKernelGGL(rg_emit_kernel, dim3(blocks(E)), dim3(256), 0, st, E, n, (int)dim, (const unsigned long long *)d_pk_s, points_dev,
+                       pairs_dev, coords_dev);
+    AMP_LAUNCH_CHECK();
+    AMP_HIP(hipStreamSynchronize(st));   // scratch dies with this scope
+    return 0;
+}
+
+} // namespace amp
+
+extern "C" int athena_mp_radius_pairs(int32_t n, int32_t dim, const float *points_dev, float radius, int32_t *pairs_dev,
+                                      float *coords_dev, int64_t capacity, int64_t *n_pairs_out)
+{
+    return amp::radius_pairs_core(n, dim, points_dev, radius, pairs_dev, coords_dev, capacity, n_pairs_out);
+}
+
+extern "C" int athena_mp_radius_graph_host(int32_t n, int32_t dim, const float *points_host, float radius, int32_t add_self_loops,
+                                           int32_t *adj_ia_out, int32_t *adj_ja_out, int64_t capacity, int64_t *nnz_out,
+                                           float *coords_out, int64_t coords_capacity, int64_t *n_pairs_out)
+{
+    AMP_REQUIRE(nnz_out != nullptr && n_pairs_out != nullptr, "radius_graph_host: null output pointer");
+    *nnz_out = *n_pairs_out = 0;
+    AMP_REQUIRE(n >= 0 && dim >= 1 && dim <= 3 && (n == 0 || points_host != nullptr), "radius_graph_host: bad arguments (n = %d, dim = %d)",
+                n, dim);
+    hipStream_t st = amp::stream();
+    Scratch tmp;
+    float *d_pts = nullptr, *d_coords = nullptr;
+    int32_t *d_pairs = nullptr;
+    if (tmp.get(&d_pts, (size_t)n * dim)) return 1;
+    if (n > 0) AMP_HIP(hipMemcpyAsync(d_pts, points_host, sizeof(float) * (size_t)n * dim, hipMemcpyHostToDevice, st));
+    int64_t E = 0;
+    if (int rc = amp::radius_pairs_core(n, dim, d_pts, radius, nullptr, nullptr, 0, &E)) return rc;
+    // no self pair and no duplicate pair: every pair is two entries, every vertex gets its loop when asked
+    const int64_t nnz = 2 * E + (add_self_loops ? n : 0);
+    *n_pairs_out = E;
+    *nnz_out = nnz;
+    if (adj_ja_out == nullptr) return 0;                          // size query
+    AMP_REQUIRE(adj_ia_out != nullptr && (coords_out != nullptr || E == 0), "radius_graph_host: null output array");
+    AMP_REQUIRE(capacity >= nnz, "radius_graph_host: adj_ja buffer holds %lld entries, the graph has %lld", (long long)capacity,
+                (long long)nnz);
+    AMP_REQUIRE(coords_capacity >= E, "radius_graph_host: coords buffer holds %lld pairs, the graph has %lld", (long long)coords_capacity,
+                (long long)E);
+    if (tmp.get(&d_pairs, 2 * (size_t)E) || tmp.get(&d_coords, (size_t)E * dim)) return 1;
+    if (int rc = amp::radius_pairs_core(n, dim, d_pts, radius, d_pairs, d_coords, E, &E)) return rc;
+    if (E > 0) AMP_HIP(hipMemcpyAsync(coords_out, d_coords, sizeof(float) * (size_t)E * dim, hipMemcpyDeviceToHost, st));
+    int64_t nnz_built = 0;
+    if (int rc = amp::csr_from_edges_core(n, E, d_pairs, add_self_loops, adj_ia_out, adj_ja_out, capacity, &nnz_built, nullptr, true))
+        return rc;
+    AMP_HIP(hipStreamSynchronize(st));
+    *nnz_out = nnz_built;
+    return 0;
+}

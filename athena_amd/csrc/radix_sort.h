@@ -9,6 +9,7 @@
 //                         atomics, so equal keys keep their input order, which is what makes the transposed CSR list its sources
 //                         in ascending order (the reference's scatter order, athena_diffstruc_extd_sub_kipf.f90:101-109).
 // Passes ping-pong between the output and one scratch pair; the input is never written.
+// Included by graph_build.hip and radius_graph.hip: the two kernels that are not templates are static, one copy per file.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -64,7 +65,7 @@ __device__ inline uint32_t block_exclusive_scan(uint32_t v, uint32_t *total)
 }
 
 // grid = 256 bins: the bin's row of per-tile counts becomes per-tile offsets inside the bin; bin_total[bin] = its size
-__global__ __launch_bounds__(kThreads) void radix_scan_rows(uint32_t *__restrict__ hist, uint32_t tiles, uint32_t *__restrict__ bin_total)
+static __global__ __launch_bounds__(kThreads) void radix_scan_rows(uint32_t *__restrict__ hist, uint32_t tiles, uint32_t *__restrict__ bin_total)
 {
     uint32_t *row = hist + (size_t)blockIdx.x * tiles;
     const uint32_t per = (tiles + kThreads - 1) / kThreads;
@@ -81,7 +82,7 @@ __global__ __launch_bounds__(kThreads) void radix_scan_rows(uint32_t *__restrict
     if (threadIdx.x == 0) bin_total[blockIdx.x] = total;
 }
 
-__global__ __launch_bounds__(kThreads) void radix_scan_bins(uint32_t *__restrict__ bin_total)
+static __global__ __launch_bounds__(kThreads) void radix_scan_bins(uint32_t *__restrict__ bin_total)
 {
     uint32_t total;
     bin_total[threadIdx.x] = block_exclusive_scan(bin_total[threadIdx.x], &total);

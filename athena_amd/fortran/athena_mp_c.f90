@@ -50,6 +50,7 @@ module athena_mp_c
   public :: athena_mp_duvenaud_readout_fwd, athena_mp_duvenaud_readout_bwd, athena_mp_duvenaud_update_act_fwd
   public :: athena_mp_kipf_layer_fwd, athena_mp_kipf_layer_bwd_x, athena_mp_activation_bwd
   public :: athena_mp_csr_from_edges, athena_mp_graph_export, athena_mp_graph_create_from_edges
+  public :: athena_mp_graph_create_from_edges_dev, athena_mp_radius_pairs, athena_mp_radius_graph_host
   public :: athena_mp_error_message
   public :: athena_mp_pull_gemm, athena_mp_dev_offset, athena_mp_kipf_layer_bwd
   public :: athena_mp_comm_create, athena_mp_comm_create_from_file, athena_mp_comm_destroy, athena_mp_comm_barrier
@@ -469,6 +470,41 @@ module athena_mp_c
        type(c_ptr), value :: adj_ja
        integer(c_int64_t), intent(out) :: nnz
        type(c_ptr), intent(out) :: graph
+     end function
+     !! the same for an index list that is already in HBM (index_list_dev: the pair list athena_mp_radius_pairs wrote)
+     integer(c_int) function athena_mp_graph_create_from_edges_dev(n_vertices, n_pairs, index_list_dev, add_self_loops, &
+          with_edge_ids, adj_ia, adj_ja, capacity, nnz, graph) bind(C, name="athena_mp_graph_create_from_edges_dev")
+       import :: c_int, c_int32_t, c_int64_t, c_ptr
+       integer(c_int32_t), value :: n_vertices, add_self_loops, with_edge_ids
+       integer(c_int64_t), value :: n_pairs, capacity
+       type(c_ptr), value :: index_list_dev
+       integer(c_int32_t), intent(inout) :: adj_ia(*)
+       type(c_ptr), value :: adj_ja
+       integer(c_int64_t), intent(out) :: nnz
+       type(c_ptr), intent(out) :: graph
+     end function
+     !! points (dim, n) on the device -> pair list (2, capacity) and coords (dim, capacity) on the device, pairs in
+     !! lexicographic order of (i, j), i < j; both outputs c_null_ptr: n_pairs only (definition: include/athena_mp.h)
+     integer(c_int) function athena_mp_radius_pairs(n, dim, points_dev, radius, pairs_dev, coords_dev, capacity, n_pairs) &
+          bind(C, name="athena_mp_radius_pairs")
+       import :: c_int, c_int32_t, c_int64_t, c_float, c_ptr
+       integer(c_int32_t), value :: n, dim
+       type(c_ptr), value :: points_dev, pairs_dev, coords_dev
+       real(c_float), value :: radius
+       integer(c_int64_t), value :: capacity
+       integer(c_int64_t), intent(out) :: n_pairs
+     end function
+     !! the same with host arrays: points (dim, n) -> adj_ia (n + 1), adj_ja (2, capacity), coords (dim, coords_capacity);
+     !! adj_ja = c_null_ptr queries nnz and n_pairs (adj_ia and coords may then be c_null_ptr too)
+     integer(c_int) function athena_mp_radius_graph_host(n, dim, points, radius, add_self_loops, adj_ia, adj_ja, capacity, &
+          nnz, coords, coords_capacity, n_pairs) bind(C, name="athena_mp_radius_graph_host")
+       import :: c_int, c_int32_t, c_int64_t, c_float, c_ptr
+       integer(c_int32_t), value :: n, dim, add_self_loops
+       real(c_float), intent(in) :: points(dim, *)
+       real(c_float), value :: radius
+       type(c_ptr), value :: adj_ia, adj_ja, coords     !! c_loc of adj_ia(n+1), adj_ja(2,capacity), coords(dim,coords_capacity)
+       integer(c_int64_t), value :: capacity, coords_capacity
+       integer(c_int64_t), intent(out) :: nnz, n_pairs
      end function
      !! one array of the handle back on the host (which: see include/athena_mp.h); host_dst = c_null_ptr queries count
      integer(c_int) function athena_mp_graph_export(graph, which, host_dst, capacity, count) &

@@ -156,6 +156,34 @@ class graph_type:
                    C.byref(nnz))
         self.adj_ia, self.adj_ja = ia, ja
 
+    def generate_radius_adjacency_device(self, points, radius, add_self_loops=False):
+        """The radius graph of a point cloud, built on the GPU (athena_mp_radius_graph_host): points [n, dim] float32, dim 1..3;
+        i < j are joined iff the fp32 sum of the squared fp32 differences is <= fl(radius * radius); edge ids follow the
+        lexicographic order of (i, j).  Sets num_vertices (when unset), num_edges, adj_ia, adj_ja -- the arrays
+        generate_adjacency (+ add_self_loops) makes of that pair list -- and returns coords [num_edges, dim] = p_i - p_j
+        (numpy), graph_nop_layer_type's edge input.  The sibling of generate_adjacency_device."""
+        pts = np.ascontiguousarray(points, dtype=np.float32)
+        if pts.ndim != 2:
+            raise ValueError("points must be [n, dim]")
+        n, dim = pts.shape
+        if self.num_vertices == 0:
+            self.num_vertices = n
+        if n != self.num_vertices:
+            raise ValueError("points must hold one row per vertex")
+        _capi.init(0)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        nnz, E = C.c_int64(), C.c_int64()
+        _capi.call("athena_mp_radius_graph_host", n, dim, vp(pts), float(radius), int(bool(add_self_loops)), None, None, 0,
+                   C.byref(nnz), None, 0, C.byref(E))
+        ia = np.empty(n + 1, np.int32)
+        ja = np.empty((2, nnz.value), np.int32, order="F")
+        coords = np.empty((E.value, dim), np.float32)
+        _capi.call("athena_mp_radius_graph_host", n, dim, vp(pts), float(radius), int(bool(add_self_loops)), vp(ia), vp(ja),
+                   nnz.value, C.byref(nnz), vp(coords), E.value, C.byref(E))
+        self.num_edges = int(E.value)
+        self.adj_ia, self.adj_ja = ia, ja
+        return coords
+
     def add_self_loops(self):
         """A~ = A + I: one entry (v, v) with edge id 0 per vertex that has none."""
         rows = np.repeat(np.arange(1, self.num_vertices + 1), np.diff(self.adj_ia))
@@ -279,6 +307,47 @@ class DeviceGraph:
         if want_adjacency:
             return self, ia, np.asfortranarray(ja[:, :self.nnz])
         return self
+
+    @classmethod
+    def from_points(cls, points, radius, add_self_loops=False, want_adjacency=False, device=0):
+        """points -> radius graph -> device handle without the pair list leaving HBM (athena_mp_radius_pairs, then
+        athena_mp_graph_create_from_edges_dev).  points [n, dim] float32, dim 1..3: a numpy array, or a torch tensor that is
+        already on the device (then only adj_ia crosses PCIe, unless the adjacency is asked for).  Returns
+        (handle, coords) or (handle, coords, adj_ia, adj_ja); coords is a device tensor [num_edges, dim] = p_i - p_j, i < j,
+        rows in lexicographic order of (i, j): graph_nop_layer_type's edge input for this handle."""
+        import torch
+
+        _capi.init(device)
+        dev = torch.device("cuda", device)
+        if isinstance(points, torch.Tensor):
+            pts = points.to(dev, torch.float32).contiguous()
+        else:
+            pts = torch.from_numpy(np.ascontiguousarray(points, dtype=np.float32)).to(dev)
+        if pts.dim() != 2:
+            raise ValueError("points must be [n, dim]")
+        n, dim = int(pts.shape[0]), int(pts.shape[1])
+        _capi.use_torch_stream()
+        ptr = lambda t: C.c_void_p(t.data_ptr())
+        E = C.c_int64()
+        _capi.call("athena_mp_radius_pairs", n, dim, ptr(pts), float(radius), None, None, 0, C.byref(E))
+        pairs = torch.empty((E.value, 2), dtype=torch.int32, device=dev)       # the memory of a column-major [2, E]
+        coords = torch.empty((E.value, dim), dtype=torch.float32, device=dev)
+        _capi.call("athena_mp_radius_pairs", n, dim, ptr(pts), float(radius), ptr(pairs), ptr(coords), E.value, C.byref(E))
+        self = cls.__new__(cls)
+        ia = np.empty(n + 1, np.int32)
+        nnz = C.c_int64()
+        h = C.c_void_p()
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        ja = np.empty((2, 2 * E.value + n), np.int32, order="F") if want_adjacency else None
+        _capi.call("athena_mp_graph_create_from_edges_dev", n, E.value, ptr(pairs), int(bool(add_self_loops)), 1, vp(ia),
+                   vp(ja) if ja is not None else None, ja.shape[1] if ja is not None else 0, C.byref(nnz), C.byref(h))
+        self.handle = h
+        self.n_rows = self.n_cols = n
+        self.nnz = int(nnz.value)
+        self.n_edge_cols = int(E.value)
+        if want_adjacency:
+            return self, coords, ia, np.asfortranarray(ja[:, :self.nnz])
+        return self, coords
 
     @classmethod
     def borrow(cls, handle, owner=None):

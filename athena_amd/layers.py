@@ -163,6 +163,20 @@ class msgpass_layer_type:
         self._set_cut(vo.copy(), True)
         return self
 
+    def set_graph_handle(self, handle):
+        """One graph that exists only as a device handle (DeviceGraph.from_points / from_edges: built in HBM, no graph_type
+        on the host): the layer runs on it as one sample; the caller keeps the handle alive and closes it."""
+        import types
+
+        vo = np.array([0, handle.n_rows], np.int32)
+        self.graph = types.SimpleNamespace(device=handle, num_vertices=handle.n_rows, num_edges=handle.n_edge_cols,
+                                           vertex_offsets=vo, batch=1)
+        self._graph_key = self._graph_refs = None
+        self._own_offsets = vo
+        self._cut = None
+        self._set_cut(vo, False)
+        return self
+
     # -- text card of the network file (print_base / read) -------------------------------------------
     def print(self, file=None):
         """the layer's card as athena writes it (athena_base_layer_sub_io.f90:14-65); appended to `file` if given"""

@@ -103,6 +103,31 @@ int athena_mp_graph_create_from_edges(int32_t n_vertices, int64_t n_pairs, const
                                       int32_t add_self_loops, int32_t with_edge_ids, int32_t *adj_ia_out,
                                       int32_t *adj_ja_out, int64_t capacity, int64_t *nnz_out,
                                       athena_mp_graph **out);
+/* athena_mp_graph_create_from_edges for an index list that is ALREADY IN HBM (the pair list athena_mp_radius_pairs wrote):
+ * same arguments otherwise, same results, nothing uploaded. */
+int athena_mp_graph_create_from_edges_dev(int32_t n_vertices, int64_t n_pairs, const int32_t *index_list_dev,
+                                          int32_t add_self_loops, int32_t with_edge_ids, int32_t *adj_ia_out,
+                                          int32_t *adj_ja_out, int64_t capacity, int64_t *nnz_out,
+                                          athena_mp_graph **out);
+/* Points -> radius graph on the device (radius_graph.hip): the pair list and the edge geometry graph_nop_layer_type works on
+ * (its inputs, athena_graph_nop_layer.f90:743-758).  graphstruc has no such call; the step in front of the two builders above.
+ *   points [n, dim] fp32 row-major, dim in 1..3; radius fp32 > 0.
+ *   delta = p_i - p_j per component in fp32, s = ((d0*d0) + d1*d1) + d2*d2, every multiply and add rounded to fp32 on its own;
+ *   i < j are joined iff s <= fl(radius * radius).  No self pairs; two points at the same place are joined.
+ *   Pairs are numbered in lexicographic order of (i, j), i < j: pairs [2, capacity] column-major, 1-based (the index_list
+ *   of the builders, column = edge id); coords [capacity, dim], coords[e, :] = p_i - p_j (smaller index minus larger).
+ * Everything stays in HBM.  pairs_dev == NULL && coords_dev == NULL: size query (the count pass only), as
+ * athena_mp_csr_from_edges.  Either of the two may be NULL alone.  Refused with a message: dim outside 1..3, a radius that is
+ * not finite or <= 0, a non-finite coordinate (the first such point is named), 2 * pairs + n >= 2^31 (found by the count
+ * pass, before anything of that size is allocated), capacity < pairs.  Two builds of the same points are byte-identical. */
+int athena_mp_radius_pairs(int32_t n, int32_t dim, const float *points_dev, float radius, int32_t *pairs_dev,
+                           float *coords_dev, int64_t capacity, int64_t *n_pairs_out);
+/* The same with every array on the host, for callers that hold Fortran arrays: points -> adj_ia [n+1], adj_ja [2, capacity]
+ * column-major (what generate_adjacency [+ add_self_loops] makes of the pair list: the neighbours of every row ascend) and
+ * coords [coords_capacity, dim].  adj_ja_out == NULL: size query for both counts (*nnz_out, *n_pairs_out). */
+int athena_mp_radius_graph_host(int32_t n, int32_t dim, const float *points_host, float radius, int32_t add_self_loops,
+                                int32_t *adj_ia_out, int32_t *adj_ja_out, int64_t capacity, int64_t *nnz_out,
+                                float *coords_out, int64_t coords_capacity, int64_t *n_pairs_out);
 int athena_mp_graph_export(const athena_mp_graph *g, int32_t which, void *host_dst, int64_t capacity,
                            int64_t *count);
 int athena_mp_graph_destroy(athena_mp_graph *g);
