@@ -11,7 +11,7 @@
 // How: a uniform grid whose cells are at least radius * (1 + 2^-10) wide on every axis, at most kMaxCellsAxis cells per axis and
 // at most 2 n cells in all; a stable radix sort of (cell, point id) (radix_sort.h), the positions copied into cell order; a COUNT
 // pass in which every point counts its partners with a larger id in the 3^dim cells around it; an exclusive scan of the counts
-// IN POINT-ID ORDER (64-bit offsets), so the rows of the pair list already sit in lexicographic order of i; a FILL pass that
+// IN POINT-ID ORDER (64-bit offsets, scan64.h), so the rows of the pair list already sit in lexicographic order of i; a FILL pass that
 // writes the keys i * n + j into those rows; one radix sort of the keys, which puts the partners of every row in ascending
 // order; one pass that decodes the keys into the 1-based pair list and the coordinate differences.  No atomics on data: counts,
 // offsets and the final order are functions of the input alone.
@@ -27,6 +27,7 @@
 
 #include "common.h"
 #include "radix_sort.h"
+#include "scan64.h"
 
 namespace {
 
@@ -207,81 +208,6 @@ __global__ __launch_bounds__(256) void rg_neighbour_kernel(int32_t n, Grid g, fl
     if (!FILL) count[i] = found;
 }
 
-// ---- exclusive scan of the counts in point-id order, 64-bit offsets ----------------------------------------------------------
-constexpr int kScanPer = 16;
-constexpr int kScanTile = 256 * kScanPer;
-
-__device__ inline unsigned long long block_scan64(unsigned long long v, unsigned long long *total)
-{
-    __shared__ unsigned long long wsum[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned long long inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned long long up = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += up;
-    }
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    unsigned long long off = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-        if (w < wave) off += wsum[w];
-        all += wsum[w];
-    }
-    __syncthreads();
-    *total = all;
-    return off + inc - v;
-}
-
-__global__ __launch_bounds__(256) void rg_tile_sum_kernel(int32_t n, const uint32_t *__restrict__ count,
-                                                          unsigned long long *__restrict__ tile_sum)
-{
-    const int64_t base = (int64_t)blockIdx.x * kScanTile + (int64_t)threadIdx.x * kScanPer;
-    unsigned long long s = 0;
-    for (int k = 0; k < kScanPer; ++k)
-        if (base + k < n) s += count[base + k];
-    unsigned long long total;
-    (void)block_scan64(s, &total);
-    if (threadIdx.x == 0) tile_sum[blockIdx.x] = total;
-}
-
-// one block: tile_sum becomes the tiles' exclusive offsets, tile_sum[tiles] the grand total
-__global__ __launch_bounds__(256) void rg_scan_tiles_kernel(uint32_t tiles, unsigned long long *__restrict__ tile_sum)
-{
-    unsigned long long carry = 0;
-    for (uint32_t base = 0; base < tiles; base += 256) {
-        const uint32_t t = base + threadIdx.x;
-        const unsigned long long v = t < tiles ? tile_sum[t] : 0ull;
-        unsigned long long total;
-        const unsigned long long ex = block_scan64(v, &total);
-        if (t < tiles) tile_sum[t] = carry + ex;
-        carry += total;
-    }
-    if (threadIdx.x == 0) tile_sum[tiles] = carry;
-}
-
-__global__ __launch_bounds__(256) void rg_scan_apply_kernel(int32_t n, const uint32_t *__restrict__ count,
-                                                            const unsigned long long *__restrict__ tile_off,
-                                                            unsigned long long *__restrict__ offset)
-{
-    const int64_t base = (int64_t)blockIdx.x * kScanTile + (int64_t)threadIdx.x * kScanPer;
-    uint32_t c[kScanPer];
-    unsigned long long s = 0;
-#pragma unroll
-    for (int k = 0; k < kScanPer; ++k) {
-        c[k] = base + k < n ? count[base + k] : 0u;
-        s += c[k];
-    }
-    unsigned long long total;
-    unsigned long long run = tile_off[blockIdx.x] + block_scan64(s, &total);
-#pragma unroll
-    for (int k = 0; k < kScanPer; ++k) {
-        if (base + k < n) offset[base + k] = run;
-        run += c[k];
-    }
-}
-
 // ---- sorted keys -> 1-based pair list [2, E] column-major and coords [E, dim] -------------------------------------------------
 __global__ __launch_bounds__(256) void rg_emit_kernel(int64_t E, int32_t n, int dim, const unsigned long long *__restrict__ key,
                                                       const float *__restrict__ pts, int32_t *__restrict__ pairs,
@@ -388,7 +314,7 @@ int radius_pairs_core(int32_t n, int32_t dim, const float *points_dev, float rad
     float *d_sorted = nullptr;
     unsigned long long *d_tile = nullptr, *d_offset = nullptr;
     void *d_temp = nullptr;
-    const uint32_t tiles = (uint32_t)(((int64_t)n + kScanTile - 1) / kScanTile);
+    const uint32_t tiles = scan64::tiles(n);
     if (tmp.get(&d_key, n) || tmp.get(&d_key_s, n) || tmp.get(&d_key_t, n) || tmp.get(&d_perm, n) || tmp.get(&d_perm_t, n) ||
         tmp.get(&d_cell_start, (size_t)n_cells + 1) || tmp.get(&d_sorted, (size_t)n * dim) || tmp.get(&d_count, n) ||
         tmp.get(&d_tile, (size_t)tiles + 1) || tmp.get((char **)&d_temp, radix::scratch_bytes(n)))
@@ -404,8 +330,8 @@ int radius_pairs_core(int32_t n, int32_t dim, const float *points_dev, float rad
                        d_cell_start);
     launch_neighbour<false>(dim, n, st, grid, r2, (const float *)d_sorted, (const int32_t *)d_perm, (const uint32_t *)d_key_s,
                             (const int32_t *)d_cell_start, d_count, (const unsigned long long *)nullptr, (unsigned long long *)nullptr);
-    hipLaunchKernelGGL(rg_tile_sum_kernel, dim3(tiles), dim3(256), 0, st, n, (const uint32_t *)d_count, d_tile);
-    hipLaunchKernelGGL(rg_scan_tiles_kernel, dim3(1), dim3(256), 0, st, tiles, d_tile);
+    hipLaunchKernelGGL(scan64::tile_sum_kernel<uint32_t>, dim3(tiles), dim3(256), 0, st, (int64_t)n, (const uint32_t *)d_count, d_tile);
+    hipLaunchKernelGGL(scan64::scan_tiles_kernel, dim3(1), dim3(256), 0, st, tiles, d_tile);
     AMP_LAUNCH_CHECK();
     unsigned long long total = 0;
     AMP_HIP(hipMemcpyAsync(&total, d_tile + tiles, sizeof(total), hipMemcpyDeviceToHost, st));
@@ -426,7 +352,7 @@ int radius_pairs_core(int32_t n, int32_t dim, const float *points_dev, float rad
     if (tmp.get(&d_offset, n) || tmp.get(&d_pk, E) || tmp.get(&d_pk_s, E) || tmp.get(&d_pk_t, E) || tmp.get(&d_v, E) || tmp.get(&d_v_t, E) ||
         tmp.get((char **)&d_temp2, radix::scratch_bytes(E)))
         return 1;
-    hipLaunchKernelGGL(rg_scan_apply_kernel, dim3(tiles), dim3(256), 0, st, n, (const uint32_t *)d_count,
+    hipLaunchKernelGGL(scan64::apply_kernel<uint32_t>, dim3(tiles), dim3(256), 0, st, (int64_t)n, (const uint32_t *)d_count,
                        (const unsigned long long *)d_tile, d_offset);
     launch_neighbour<true>(dim, n, st, grid, r2, (const float *)d_sorted, (const int32_t *)d_perm, (const uint32_t *)d_key_s,
                            (const int32_t *)d_cell_start, (uint32_t *)nullptr, (const unsigned long long *)d_offset, d_pk);

@@ -51,6 +51,7 @@ module athena_mp_c
   public :: athena_mp_kipf_layer_fwd, athena_mp_kipf_layer_bwd_x, athena_mp_activation_bwd
   public :: athena_mp_csr_from_edges, athena_mp_graph_export, athena_mp_graph_create_from_edges
   public :: athena_mp_graph_create_from_edges_dev, athena_mp_radius_pairs, athena_mp_radius_graph_host
+  public :: athena_mp_periodic_pairs, athena_mp_periodic_graph_host
   public :: athena_mp_error_message
   public :: athena_mp_pull_gemm, athena_mp_dev_offset, athena_mp_kipf_layer_bwd
   public :: athena_mp_comm_create, athena_mp_comm_create_from_file, athena_mp_comm_destroy, athena_mp_comm_barrier
@@ -504,6 +505,38 @@ module athena_mp_c
        real(c_float), value :: radius
        type(c_ptr), value :: adj_ia, adj_ja, coords     !! c_loc of adj_ia(n+1), adj_ja(2,capacity), coords(dim,coords_capacity)
        integer(c_int64_t), value :: capacity, coords_capacity
+       integer(c_int64_t), intent(out) :: nnz, n_pairs
+     end function
+     !! periodic structures -> pair list and edge geometry on the device, a batch per call (replaces get_graph_from_basis;
+     !! definition: include/athena_mp.h).  offsets (n_structures + 1) and pbc (3) on the host; frac (3, n_atoms) and
+     !! lat (3, 3, n_structures) -- lat(c, a, s) = component c of lattice vector a, i.e. transpose(basis%lat) -- on the device;
+     !! outputs on the device: pairs (2, capacity), feature (capacity), vec (3, capacity), shift (3, capacity),
+     !! first_count (n_atoms), each may be c_null_ptr; all five c_null_ptr: n_pairs only.  edge_offsets: c_loc of an
+     !! integer(c_int64_t) (n_structures + 1) host array, or c_null_ptr
+     integer(c_int) function athena_mp_periodic_pairs(n_structures, n_atoms, offsets, frac_dev, lat_dev, pbc, cutoff_min, &
+          cutoff_max, pairs_dev, feature_dev, vec_dev, shift_dev, first_count_dev, capacity, n_pairs, edge_offsets) &
+          bind(C, name="athena_mp_periodic_pairs")
+       import :: c_int, c_int32_t, c_int64_t, c_float, c_ptr
+       integer(c_int32_t), value :: n_structures, n_atoms
+       integer(c_int32_t), intent(in) :: offsets(*), pbc(3)
+       type(c_ptr), value :: frac_dev, lat_dev, pairs_dev, feature_dev, vec_dev, shift_dev, first_count_dev, edge_offsets
+       real(c_float), value :: cutoff_min, cutoff_max
+       integer(c_int64_t), value :: capacity
+       integer(c_int64_t), intent(out) :: n_pairs
+     end function
+     !! the same with host arrays: -> adj_ia (n_atoms + 1), adj_ja (2, capacity), feature (edge_capacity),
+     !! vec (3, edge_capacity), first_count (n_atoms), edge_offsets (n_structures + 1, int64), all passed as c_loc;
+     !! adj_ja = c_null_ptr queries nnz and n_pairs (the other outputs may then be c_null_ptr too)
+     integer(c_int) function athena_mp_periodic_graph_host(n_structures, n_atoms, offsets, frac, lat, pbc, cutoff_min, &
+          cutoff_max, add_self_loops, adj_ia, adj_ja, capacity, nnz, feature, vec, first_count, edge_capacity, n_pairs, &
+          edge_offsets) bind(C, name="athena_mp_periodic_graph_host")
+       import :: c_int, c_int32_t, c_int64_t, c_float, c_ptr
+       integer(c_int32_t), value :: n_structures, n_atoms, add_self_loops
+       integer(c_int32_t), intent(in) :: offsets(*), pbc(3)
+       real(c_float), intent(in) :: frac(3, *), lat(3, 3, *)
+       real(c_float), value :: cutoff_min, cutoff_max
+       type(c_ptr), value :: adj_ia, adj_ja, feature, vec, first_count, edge_offsets
+       integer(c_int64_t), value :: capacity, edge_capacity
        integer(c_int64_t), intent(out) :: nnz, n_pairs
      end function
      !! one array of the handle back on the host (which: see include/athena_mp.h); host_dst = c_null_ptr queries count

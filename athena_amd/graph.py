@@ -18,6 +18,22 @@ import numpy as np
 from . import _capi
 
 
+def _structure_arrays(frac, lat, offsets, pbc):
+    """the inputs of the periodic builders as the C ABI takes them: frac [n, 3] / lat [B, 3, 3] float32, offsets [B + 1] and
+    pbc [3] int32 on the host"""
+    off = np.ascontiguousarray(offsets, dtype=np.int32)
+    pbc3 = np.ascontiguousarray([1 if p else 0 for p in pbc], dtype=np.int32)
+    if not (off.ndim == 1 and off.size >= 1 and pbc3.size == 3):
+        raise ValueError("offsets must be [B + 1] and pbc three flags")
+    if isinstance(frac, np.ndarray) or not hasattr(frac, "data_ptr"):
+        frac = np.ascontiguousarray(frac, dtype=np.float32).reshape(-1, 3)
+    if isinstance(lat, np.ndarray) or not hasattr(lat, "data_ptr"):
+        lat = np.ascontiguousarray(lat, dtype=np.float32).reshape(-1, 3, 3)
+    if not (lat.shape[0] == off.size - 1 and tuple(lat.shape[1:]) == (3, 3) and frac.shape[-1] == 3 and len(frac.shape) == 2):
+        raise ValueError("frac must be [n, 3] and lat [B, 3, 3] with B + 1 offsets")
+    return frac, lat, off, pbc3
+
+
 class graph_type:
     """Undirected sparse graph in athena's CSR convention."""
 
@@ -184,6 +200,36 @@ class graph_type:
         self.adj_ia, self.adj_ja = ia, ja
         return coords
 
+    def generate_periodic_adjacency_device(self, frac, lat, offsets, cutoff_min, cutoff_max, pbc=(1, 1, 1), add_self_loops=False):
+        """The neighbour graphs of a batch of periodic structures as ONE block-diagonal graph, built on the GPU
+        (athena_mp_periodic_graph_host; the definition is in include/athena_mp.h): frac [n, 3] float32 fractional coordinates,
+        lat [B, 3, 3] float32 (row a = lattice vector a), offsets [B + 1] 0-based.  What get_graph_from_basis + generate_adjacency
+        (+ add_self_loops) make of every structure, edge ids running over the batch.  Sets num_vertices (when unset), num_edges,
+        adj_ia, adj_ja and returns (feature [E] = r / cutoff_max, vec [E, 3], first_count [n], edge_offsets [B + 1]) as numpy.
+        The host-array sibling of DeviceGraph.from_structures."""
+        frac, lat, off, pbc3 = _structure_arrays(frac, lat, offsets, pbc)
+        n, B = frac.shape[0], lat.shape[0]
+        if self.num_vertices == 0:
+            self.num_vertices = n
+        if n != self.num_vertices:
+            raise ValueError("frac must hold one row per vertex")
+        _capi.init(0)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        nnz, E = C.c_int64(), C.c_int64()
+        head = (B, n, vp(off), vp(frac), vp(lat), vp(pbc3), float(cutoff_min), float(cutoff_max), int(bool(add_self_loops)))
+        _capi.call("athena_mp_periodic_graph_host", *head, None, None, 0, C.byref(nnz), None, None, None, 0, C.byref(E), None)
+        ia = np.empty(n + 1, np.int32)
+        ja = np.empty((2, nnz.value), np.int32, order="F")
+        feature = np.empty(E.value, np.float32)
+        vec = np.empty((E.value, 3), np.float32)
+        first = np.empty(n, np.int32)
+        eoff = np.empty(B + 1, np.int64)
+        _capi.call("athena_mp_periodic_graph_host", *head, vp(ia), vp(ja), nnz.value, C.byref(nnz), vp(feature), vp(vec), vp(first),
+                   E.value, C.byref(E), vp(eoff))
+        self.num_edges = int(E.value)
+        self.adj_ia, self.adj_ja = ia, ja
+        return feature, vec, first, eoff
+
     def add_self_loops(self):
         """A~ = A + I: one entry (v, v) with edge id 0 per vertex that has none."""
         rows = np.repeat(np.arange(1, self.num_vertices + 1), np.diff(self.adj_ia))
@@ -348,6 +394,52 @@ class DeviceGraph:
         if want_adjacency:
             return self, coords, ia, np.asfortranarray(ja[:, :self.nnz])
         return self, coords
+
+    @classmethod
+    def from_structures(cls, frac, lat, offsets, cutoff_min, cutoff_max, pbc=(1, 1, 1), add_self_loops=False, want_adjacency=False,
+                        device=0):
+        """A batch of periodic structures -> one block-diagonal device handle without the pair list leaving HBM
+        (athena_mp_periodic_pairs, then athena_mp_graph_create_from_edges_dev): what the reference's get_graph_from_basis +
+        generate_adjacency (+ add_self_loops) make of every structure, on the host, one at a time.  frac [n, 3] fractional
+        coordinates and lat [B, 3, 3] (row a = lattice vector a): float32 numpy arrays, or torch tensors already on the device;
+        offsets [B + 1] 0-based on the host; pbc: an axis with 0 is neither wrapped nor imaged.  The definition of the edges
+        (fp32, term by term) is in include/athena_mp.h.  Returns (handle, feature, vec, vertex_offsets, edge_offsets) or, with
+        want_adjacency, (..., adj_ia, adj_ja): feature [E] = r / cutoff_max and vec [E, 3] = atom i minus the image of atom j
+        are device tensors, rows in edge-id order; vertex_offsets (int32) and edge_offsets (int64) are numpy [B + 1] -- what
+        msgpass_layer_type.set_graph_handle(handle, vertex_offsets) cuts the batch by."""
+        import torch
+
+        _capi.init(device)
+        dev = torch.device("cuda", device)
+        frac, lat, off, pbc3 = _structure_arrays(frac, lat, offsets, pbc)
+        on_dev = lambda a: (a if isinstance(a, torch.Tensor) else torch.from_numpy(a)).to(dev, torch.float32).contiguous()
+        frac, lat = on_dev(frac), on_dev(lat)
+        n, B = int(frac.shape[0]), int(lat.shape[0])
+        _capi.use_torch_stream()
+        ptr = lambda t: C.c_void_p(t.data_ptr())
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        E = C.c_int64()
+        head = (B, n, vp(off), ptr(frac), ptr(lat), vp(pbc3), float(cutoff_min), float(cutoff_max))
+        _capi.call("athena_mp_periodic_pairs", *head, None, None, None, None, None, 0, C.byref(E), None)
+        pairs = torch.empty((E.value, 2), dtype=torch.int32, device=dev)       # the memory of a column-major [2, E]
+        feature = torch.empty(E.value, dtype=torch.float32, device=dev)
+        vec = torch.empty((E.value, 3), dtype=torch.float32, device=dev)
+        eoff = np.empty(B + 1, np.int64)
+        _capi.call("athena_mp_periodic_pairs", *head, ptr(pairs), ptr(feature), ptr(vec), None, None, E.value, C.byref(E), vp(eoff))
+        self = cls.__new__(cls)
+        ia = np.empty(n + 1, np.int32)
+        nnz = C.c_int64()
+        h = C.c_void_p()
+        ja = np.empty((2, 2 * E.value + n), np.int32, order="F") if want_adjacency else None
+        _capi.call("athena_mp_graph_create_from_edges_dev", n, E.value, ptr(pairs), int(bool(add_self_loops)), 1, vp(ia),
+                   vp(ja) if ja is not None else None, ja.shape[1] if ja is not None else 0, C.byref(nnz), C.byref(h))
+        self.handle = h
+        self.n_rows = self.n_cols = n
+        self.nnz = int(nnz.value)
+        self.n_edge_cols = int(E.value)
+        if want_adjacency:
+            return self, feature, vec, off.copy(), eoff, ia, np.asfortranarray(ja[:, :self.nnz])
+        return self, feature, vec, off.copy(), eoff
 
     @classmethod
     def borrow(cls, handle, owner=None):

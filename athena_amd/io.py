@@ -16,7 +16,12 @@ example/msgpass_chemical/pytorch_network.py:372- reads:
 block-diagonal CSR (vertex and edge ids offset per graph) plus the per-graph vertex offsets the readout
 needs -- one device graph handle and one launch per op instead of a host loop over ~130 k tiny graphs
 (SURVEY.md 8a row a10).
+
+`read_extxyz` reads the periodic structures the chemical examples start from (example/msgpass_chemical/database.xyz) and
+`cartesian_to_fractional` turns them into the input of DeviceGraph.from_structures.
 """
+import re
+
 import numpy as np
 
 from .graph import graph_type
@@ -97,6 +102,74 @@ def batch_graphs(graphs):
     x = np.concatenate([np.asarray(g.vertex_features, np.float32).reshape(g.num_vertices, -1) for g in graphs]) if S else None
     e = np.concatenate([np.asarray(g.edge_features, np.float32).reshape(g.num_edges, -1) for g in graphs]) if S else None
     return ia, ja, voff.astype(np.int32), x, e
+
+
+# ---- extended XYZ, the layout of the reference's database.xyz ------------------------------------------------------------
+# per frame:  <natoms> / Lattice="9 numbers" Properties=species:S:1:pos:R:3:forces:R:3 energy=... pbc="T T T" / natoms atom lines
+
+_XYZ_KEY = re.compile(r'(\w+)=("[^"]*"|\S+)')
+
+
+def read_extxyz(path):
+    """Every frame of an extended-XYZ file as a dict: lattice [3, 3] float64 (row a = lattice vector a, as basis%lat), species
+    (list of str), positions [n, 3] float64 (Cartesian), forces [n, 3] float64 or None, energy (float or None), pbc (three
+    bools; all True when the header does not say).  Properties must start with species:S:1:pos:R:3; forces:R:3 is read where
+    it is listed."""
+    frames = []
+    with open(path) as f:
+        lines = f.read().splitlines()
+    at = 0
+    while at < len(lines):
+        if not lines[at].strip():
+            at += 1
+            continue
+        n = int(lines[at].split()[0])
+        if at + 2 + n > len(lines):
+            raise ValueError(f"extxyz frame {len(frames) + 1}: the file ends inside the frame")
+        head = {k.lower(): v.strip('"') for k, v in _XYZ_KEY.findall(lines[at + 1])}
+        if "lattice" not in head:
+            raise ValueError(f"extxyz frame {len(frames) + 1}: no Lattice in the comment line")
+        lattice = np.array(head["lattice"].split(), np.float64)
+        if lattice.size != 9:
+            raise ValueError(f"extxyz frame {len(frames) + 1}: Lattice needs nine numbers")
+        props = head.get("properties", "species:S:1:pos:R:3").split(":")
+        fields = [(props[k], props[k + 1], int(props[k + 2])) for k in range(0, len(props) - 2, 3)]
+        if [(a.lower(), b, c) for a, b, c in fields[:2]] != [("species", "S", 1), ("pos", "R", 3)]:
+            raise ValueError(f"extxyz frame {len(frames) + 1}: Properties must start with species:S:1:pos:R:3")
+        col, force_col = 0, None
+        for name, _, width in fields:
+            if name.lower() in ("forces", "force") and width == 3:
+                force_col = col
+            col += width
+        rows = [lines[at + 2 + k].split() for k in range(n)]
+        if any(len(r) < col for r in rows):
+            raise ValueError(f"extxyz frame {len(frames) + 1}: an atom line has fewer than {col} columns")
+        pbc = [t.upper().startswith("T") or t == "1" for t in head.get("pbc", "T T T").split()]
+        frames.append({
+            "lattice": lattice.reshape(3, 3),
+            "species": [r[0] for r in rows],
+            "positions": np.array([r[1:4] for r in rows], np.float64).reshape(n, 3),
+            "forces": None if force_col is None else np.array([r[force_col:force_col + 3] for r in rows], np.float64).reshape(n, 3),
+            "energy": float(head["energy"]) if "energy" in head else None,
+            "pbc": tuple(pbc),
+        })
+        at += 2 + n
+    return frames
+
+
+def cartesian_to_fractional(positions, lattice):
+    """pos @ inv(lat) in float64, rounded to float32: the fractional coordinates (basis%spec%atom) the periodic builders start
+    from.  The device definition begins at this float32 array; the conversion is outside it."""
+    return (np.asarray(positions, np.float64) @ np.linalg.inv(np.asarray(lattice, np.float64))).astype(np.float32)
+
+
+def structures_from_frames(frames):
+    """frames of read_extxyz -> (frac [n, 3] float32, lat [B, 3, 3] float32, offsets [B + 1] int32): the arguments of
+    DeviceGraph.from_structures / graph_type.generate_periodic_adjacency_device"""
+    offsets = np.concatenate([[0], np.cumsum([f["positions"].shape[0] for f in frames])]).astype(np.int32)
+    frac = np.concatenate([cartesian_to_fractional(f["positions"], f["lattice"]) for f in frames]) if frames else np.zeros((0, 3), np.float32)
+    lat = np.array([f["lattice"] for f in frames], np.float32).reshape(-1, 3, 3)
+    return frac.reshape(-1, 3), lat, offsets
 
 
 # ---- layer cards of athena's network file ("print" / "read" of the three message-passing layers) ------------

@@ -163,18 +163,27 @@ class msgpass_layer_type:
         self._set_cut(vo.copy(), True)
         return self
 
-    def set_graph_handle(self, handle):
-        """One graph that exists only as a device handle (DeviceGraph.from_points / from_edges: built in HBM, no graph_type
-        on the host): the layer runs on it as one sample; the caller keeps the handle alive and closes it."""
+    def set_graph_handle(self, handle, vertex_offsets=None):
+        """One graph that exists only as a device handle (DeviceGraph.from_points / from_edges / from_structures: built in HBM, no
+        graph_type on the host): the layer runs on it as one sample; the caller keeps the handle alive and closes it.  With
+        vertex_offsets [batch + 1] (0-based) the handle is a block-diagonal batch and is cut into samples exactly as
+        set_graph_batched cuts a host graph."""
         import types
 
-        vo = np.array([0, handle.n_rows], np.int32)
+        own = np.array([0, handle.n_rows], np.int32)
+        batched = vertex_offsets is not None
+        vo = own
+        if batched:
+            vo = np.ascontiguousarray(vertex_offsets, dtype=np.int32)
+            if not (vo.ndim == 1 and vo.size >= 2 and vo[0] == 0 and vo[-1] == handle.n_rows and np.all(np.diff(vo) >= 0)):
+                raise ValueError("set_graph_handle: vertex_offsets must run from 0 to the handle's vertex count, ascending")
+            vo = vo.copy()
         self.graph = types.SimpleNamespace(device=handle, num_vertices=handle.n_rows, num_edges=handle.n_edge_cols,
-                                           vertex_offsets=vo, batch=1)
+                                           vertex_offsets=own, batch=1)
         self._graph_key = self._graph_refs = None
-        self._own_offsets = vo
+        self._own_offsets = own
         self._cut = None
-        self._set_cut(vo, False)
+        self._set_cut(vo, batched)
         return self
 
     # -- text card of the network file (print_base / read) -------------------------------------------

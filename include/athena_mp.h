@@ -128,6 +128,44 @@ int athena_mp_radius_pairs(int32_t n, int32_t dim, const float *points_dev, floa
 int athena_mp_radius_graph_host(int32_t n, int32_t dim, const float *points_host, float radius, int32_t add_self_loops,
                                 int32_t *adj_ia_out, int32_t *adj_ja_out, int64_t capacity, int64_t *nnz_out,
                                 float *coords_out, int64_t coords_capacity, int64_t *n_pairs_out);
+/* Periodic structures -> neighbour graphs on the device, a batch per call (periodic_graph.hip).  It replaces get_graph_from_basis
+ * of the reference's chemical examples (example/example_library/src/mod_read_chemical_graphs.f90:196-278); the step in front of
+ * athena_mp_graph_create_from_edges_dev.
+ *   n_structures structures; offsets [n_structures + 1] on the HOST, 0-based, ascending from 0 to n_atoms; frac [n_atoms, 3] fp32
+ *   fractional coordinates; lat [n_structures, 3, 3] fp32 row-major, row a = lattice vector a (Cartesian); pbc [3] on the host,
+ *   pbc[k] = 0: axis k is open (neither wrapped nor imaged); 0 <= cutoff_min < cutoff_max.
+ * Definition, every operation rounded to fp32 on its own: for local atoms i <= j of one structure and an integer shift (a, b, c)
+ *   f_k = frac_i[k] - frac_j[k];  w_k = f_k - ceil(f_k - 0.5) on a periodic axis, w_k = f_k and only shift 0 on an open axis;
+ *   v = (w_0 + a, w_1 + b, w_2 + c);  x_c = ((v_0 * L[0][c]) + v_1 * L[1][c]) + v_2 * L[2][c];
+ *   s = ((x_0 * x_0) + x_1 * x_1) + x_2 * x_2;  r = sqrt(s), correctly rounded.
+ * The triple is an edge iff r > cutoff_min and r < cutoff_max (both strict, as the reference): never the zero-shift self pair; an
+ * atom is joined to its own images, +shift and -shift both (each one CSR entry in the builders); a pair carries one edge per image.
+ * All shifts of Z^3 on the periodic axes count: the result is defined by the predicate, not by a search range (the reference's
+ * ceiling(cutoff_max / |L_a|) loses edges of skewed cells).  Edges are ordered by structure, inside one lexicographically by
+ * (i, j, a, b, c) ascending; the 1-based rank over the batch is the edge id.  Outputs in HBM, each may be NULL:
+ *   pairs [2, capacity] column-major, 1-based global vertex ids, smaller first;  feature [capacity] = r / cutoff_max (correctly
+ *   rounded: the reference's edge feature);  vec [capacity, 3] = x (atom i minus the image of atom j, the sign of coords in
+ *   athena_mp_radius_pairs);  shift [capacity, 3];  first_count [n_atoms] = edges whose FIRST index is that vertex (j >= i only:
+ *   the reference's `degree` vertex feature).  edge_offsets_out [n_structures + 1] on the host (may be NULL): where each
+ *   structure's edge columns start.  All five device outputs NULL: the count pass only, a size query.
+ * Refused with a message that names the first offending structure where there is one: offsets not ascending from 0 to n_atoms, a
+ * non-finite coordinate or lattice entry, det(lat) zero or not finite with a periodic axis, a cutoff that is not finite,
+ * cutoff_min < 0 or cutoff_max <= cutoff_min, floor(cutoff_max |L_b x L_c| / |det L| + 1/2) above 31 on a periodic axis (the cell
+ * is too small for the cutoff), 2 * edges + n_atoms >= 2^31 (found by the count pass, before anything of that size is allocated),
+ * capacity < edges.  Two builds of the same input are byte-identical. */
+int athena_mp_periodic_pairs(int32_t n_structures, int32_t n_atoms, const int32_t *offsets_host, const float *frac_dev,
+                             const float *lat_dev, const int32_t *pbc, float cutoff_min, float cutoff_max, int32_t *pairs_dev,
+                             float *feature_dev, float *vec_dev, int32_t *shift_dev, int32_t *first_count_dev, int64_t capacity,
+                             int64_t *n_pairs_out, int64_t *edge_offsets_out);
+/* The same with every array on the host, for callers that hold Fortran arrays: structures -> adj_ia [n_atoms + 1], adj_ja
+ * [2, capacity] column-major (what generate_adjacency [+ add_self_loops] makes of the pair list), feature [edge_capacity],
+ * vec [edge_capacity, 3], first_count [n_atoms] (each of the three may be NULL) and edge_offsets.  adj_ja_out == NULL: size query
+ * for both counts (*nnz_out, *n_pairs_out) and edge_offsets. */
+int athena_mp_periodic_graph_host(int32_t n_structures, int32_t n_atoms, const int32_t *offsets_host, const float *frac_host,
+                                  const float *lat_host, const int32_t *pbc, float cutoff_min, float cutoff_max,
+                                  int32_t add_self_loops, int32_t *adj_ia_out, int32_t *adj_ja_out, int64_t capacity,
+                                  int64_t *nnz_out, float *feature_out, float *vec_out, int32_t *first_count_out,
+                                  int64_t edge_capacity, int64_t *n_pairs_out, int64_t *edge_offsets_out);
 int athena_mp_graph_export(const athena_mp_graph *g, int32_t which, void *host_dst, int64_t capacity,
                            int64_t *count);
 int athena_mp_graph_destroy(athena_mp_graph *g);
