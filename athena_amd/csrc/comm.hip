@@ -529,6 +529,15 @@ __global__ void halo_add_rows_kernel(const float *__restrict__ recv, const int32
     v4 *o = reinterpret_cast<v4 *>(y + dst * F + 4 * c);
     *o = *o + a;
 }
+// the same sums value by value: a y that is not 16-byte aligned (the caller's array; recv is the library's)
+__global__ void halo_add_rows_scalar_kernel(const float *__restrict__ recv, const int32_t *__restrict__ idx, int64_t n, int F, float *__restrict__ y)
+{
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n * F) return;
+    const int64_t r = t / F;
+    float *dst = y + (idx ? (int64_t)idx[r] : r) * F + (t - r * F);
+    *dst = *dst + recv[t];
+}
 
 extern "C" {
 
@@ -1433,9 +1442,10 @@ int athena_mp_halo_reduce_finish(athena_mp_shard *s, int32_t slot, float *y_loca
         if (rows == 0) continue;
         const float *src = s->red_buf[slot] + (size_t)(s->mode == 1 ? s->max_n * (int64_t)p : s->soff[p]) * F;
         const int32_t *idx = s->mode == 1 ? nullptr : s->send_idx + s->soff[p];
-        const int64_t threads = rows * (F / 4);
-        hipLaunchKernelGGL(halo_add_rows_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, amp::stream(), src, idx, rows, F,
-                           y_local_dev);
+        const bool vec = amp::aligned16(y_local_dev);
+        const int64_t threads = rows * (vec ? F / 4 : F);
+        hipLaunchKernelGGL(vec ? halo_add_rows_kernel : halo_add_rows_scalar_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0,
+                           amp::stream(), src, idx, rows, F, y_local_dev);
         AMP_LAUNCH_CHECK();
     }
     return 0;

@@ -39,6 +39,12 @@ int aux_stream(hipStream_t *s, hipEvent_t **events);
 
 #define AMP_LAUNCH_CHECK() AMP_HIP(hipGetLastError())
 
+// The alignment contract (include/athena_mp.h): a caller's device pointer needs only the alignment of its element type.  A route
+// whose kernel goes through 16-byte accesses on a caller's array (v4f casts, b128 buffer loads / stores, nontemporal v4f stores)
+// carries this term in its host-side predicate; a call that fails it takes the entry's generic route.  Null (an absent
+// operand) constrains nothing.
+template <typename... P> inline bool aligned16(const P *...p) { return ((... | (uintptr_t)p) & 15) == 0; }
+
 // workspace owned by the library (grown on demand, never shrunk; stream-ordered reuse); per device
 int workspace(void **ptr, size_t bytes, int slot = 0);
 // hand a slot's memory back to the device (after the stream drained); the next workspace() call of that slot allocates again

@@ -1337,6 +1337,7 @@ int launch_rows(const athena_mp_graph *g, const float *X, int K, const float *W,
     // split input rows: ONE instantiation, <5, 4, readout> (the 96-wide one spills inside its tile loop: scripts/isa_lint.py R2)
     if (XT && !(kj == 5 && ot == 4 && ro)) return -1;
     if ((K & 3) || (NO & 3) || !frag_shape(kj, ot)) return -1;
+    if (!amp::aligned16(X, XT, Y) || (ro && !amp::aligned16(ro->P))) return -1;   // rows move 16 bytes per lane (W and R value by value)
     const int nt = g->n_btiles;
     if (nt == 0) return 0;
     if ((int)g->btile_off.size() - 1 > kMaxBuckets) return -1;
@@ -1411,7 +1412,7 @@ int duv_mfma_bwd_a(const athena_mp_graph *g, int Fi, int Fo, const float *grad, 
 int duv_mfma_bwd_w(const athena_mp_graph *g, int Fi, int Fo, const float *grad, const float *a, float *dw)
 {
     const int it = ceil16(Fi), ot = ceil16(Fo);
-    if ((Fi & 3) || (Fo & 3) || !frag_shape(it, ot)) return -1;
+    if ((Fi & 3) || (Fo & 3) || !frag_shape(it, ot) || !aligned16(grad, a)) return -1;
     const int nt = g->n_btiles, nb = (int)g->btile_off.size() - 1, n = Fi * Fo;
     if (nt == 0) {
         AMP_HIP(hipMemsetAsync(dw, 0, sizeof(float) * (size_t)nb * n, stream()));
@@ -1463,7 +1464,7 @@ int duv_mfma_bwd(const athena_mp_graph *g, int Fi, int Fo, const float *grad, co
 {
     if (da_tail && Fi <= 64) return -1;
     const int it = ceil16(Fi), ot = ceil16(Fo);
-    if ((Fi & 3) || (Fo & 3) || Fi < 64 || Fo < 64 || !frag_shape(it, ot)) return -1;
+    if ((Fi & 3) || (Fo & 3) || Fi < 64 || Fo < 64 || !frag_shape(it, ot) || !aligned16(grad, a, da, da_tail)) return -1;
     const int nt = g->n_btiles, nb = (int)g->btile_off.size() - 1, n = Fi * Fo;
     if (nt == 0) {
         AMP_HIP(hipMemsetAsync(dw, 0, sizeof(float) * (size_t)nb * n, stream()));
@@ -1498,6 +1499,7 @@ int duv_mfma_bwd_readout(const athena_mp_graph *g, int Fi, int Fo, int O, int ac
 {
     const int it = ceil16(Fi);
     if (!da_tail || (Fi & 3) || Fo != 64 || Fi <= 64 || it > 6 || O < 1 || O > 16 || act < 0 || act > ATHENA_MP_ACT_TANH) return -1;
+    if (!aligned16(a, a_tail, z, dz_next, da, da_tail)) return -1;
     const int nt = g->n_btiles, nb = (int)g->btile_off.size() - 1, n = Fi * Fo;
     if (nt == 0 || nb > kMaxBuckets) return -1;
     const BucketSplit sp = make_split(g, 256, 4);          // one workgroup per CU

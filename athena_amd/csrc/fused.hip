@@ -622,7 +622,8 @@ int athena_mp_kipf_layer_fwd(const athena_mp_graph *g, int32_t Fi, int32_t Fo, c
         const int rc = banded_agg_gemm64(g, false, g->coef, x, W, 0, bias, act, P, Z);
         if (rc >= 0) return rc;
     }
-    if (!banded && fused_shape(Fi, Fo) && g->lp_fwd.n_long == 0)
+    // (the one-launch kernels read x and W, and write P, 16 bytes per lane; Z and the bias go value by value)
+    if (!banded && fused_shape(Fi, Fo) && g->lp_fwd.n_long == 0 && aligned16(x, W, P))
         return fused_dispatch(g->rowptr, g->col, g->coef, x, Fi, Fo, W, 0, bias, act, P, Z, g->n_rows, g->n_cols);
     if (P == nullptr) {   // the caller keeps no tape of P (its reverse pass is athena_mp_kipf_layer_bwd)
         void *ws = nullptr;
@@ -645,7 +646,7 @@ int athena_mp_kipf_layer_bwd_x(const athena_mp_graph *g, int32_t Fi, int32_t Fo,
         const int rc = banded_agg_gemm64(g, true, exact ? g->t_coef : nullptr, dZ, W, 1, nullptr, ATHENA_MP_ACT_NONE, nullptr, dX);
         if (rc >= 0) return rc;
     }
-    if (!banded && fused_shape(Fi, Fo) && g->lp_bwd.n_long == 0) // dX = (A^T dZ) . W : aggregate, then contract with B [N=Fi][K=Fo]
+    if (!banded && fused_shape(Fi, Fo) && g->lp_bwd.n_long == 0 && aligned16(dZ, W)) // dX = (A^T dZ) . W : aggregate, then contract with B [N=Fi][K=Fo]
         return fused_dispatch(g->t_rowptr, g->t_src, exact ? g->t_coef : nullptr, dZ, Fo, Fi, W, 1, nullptr,
                               ATHENA_MP_ACT_NONE, nullptr, dX, g->n_cols, g->n_rows);
     void *ws = nullptr;
@@ -677,7 +678,7 @@ int athena_mp_kipf_layer_bwd(const athena_mp_graph *g, int32_t Fi, int32_t Fo, c
         return 0;
     }
     AMP_REQUIRE(dZ && W && X, "kipf_layer_bwd: null tensor");
-    if (amp::fused_dw_shape(Fi, Fo) && g->lp_bwd.n_long == 0 && (uintptr_t)dZ % 16 == 0 && (uintptr_t)W % 16 == 0)
+    if (amp::fused_dw_shape(Fi, Fo) && g->lp_bwd.n_long == 0 && aligned16(dZ, W))   // X, dX and dW go value by value
         return amp::fused_dw_dispatch(g->t_rowptr, g->t_src, g->t_coef, dZ, W, X, exact, dX, dW, g->n_cols);
     void *ws = nullptr;
     const size_t rows = (size_t)g->n_cols * Fo;
@@ -698,7 +699,7 @@ int athena_mp_pull_gemm(const athena_mp_graph *g, int32_t Fi, int32_t Fo, const 
     AMP_REQUIRE(g && Fi > 0 && Fo > 0, "pull_gemm: bad arguments");
     if (g->n_rows == 0) return 0;
     AMP_REQUIRE(dZ && W && dX, "pull_gemm: null tensor");
-    if (fused_shape(Fi, Fo) && g->lp_fwd.n_long == 0)
+    if (fused_shape(Fi, Fo) && g->lp_fwd.n_long == 0 && aligned16(dZ, W))
         return fused_dispatch(g->rowptr, g->col, exact ? g->coef : nullptr, dZ, Fo, Fi, W, 1, nullptr,
                               ATHENA_MP_ACT_NONE, nullptr, dX, g->n_rows, g->n_cols);
     void *ws = nullptr;

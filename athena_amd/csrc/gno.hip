@@ -479,7 +479,7 @@ int pull_dx(const athena_mp_graph *g, const int32_t *rowptr, const int32_t *idx,
     const int n = R2 * Fi;
     hipLaunchKernelGGL(gno_perm_kernel, dim3((n + 255) / 256), dim3(256), 0, amp::stream(), theta + off_V, H + 1, Fi, Fo, (float *)b2);
     AMP_LAUNCH_CHECK();
-    if (amp::gno64_shape(H, Fo, Fi, d, 4))
+    if (amp::gno64_shape(H, Fo, Fi, d, 4) && amp::aligned16(grad, dx))   // rows in and out 16 bytes per lane
         return amp::launch_gno_fused(rowptr, idx, eidx, grad, coords, theta, d, (const float *)b2, n_rows, order, dx, y_rows,
                                      g->n_edge_cols, g->nnz);
     return outer_then_contract(rowptr, idx, eidx, grad, Fo, coords, theta, d, H, n_rows, (const float *)b2, Fi, dx);
@@ -510,7 +510,7 @@ int mlp_backward_tiled(const athena_mp_graph *g, int d, int H, int Fi, int Fo, c
         if (rc) return rc;
         int nblk;
         void *sl = nullptr;
-        const bool mf = H % 32 == 0 && Fi % 32 == 0 && H <= 64 && Fi <= 64 && d <= 3;
+        const bool mf = H % 32 == 0 && Fi % 32 == 0 && H <= 64 && Fi <= 64 && d <= 3 && amp::aligned16(x);   // x rows 16 bytes per lane
         if (mf) {
             nblk = std::min((rows + 3) / 4, 512);      // 4 waves per workgroup, one slab per wave
             if (amp::workspace(&sl, sizeof(float) * (size_t)nblk * 4 * np, 3)) return 1;
@@ -551,7 +551,7 @@ int gno_mlp_backward(const athena_mp_graph *g, int d, int H, int Fi, int Fo, con
         if (amp::workspace(&p, sizeof(float) * (size_t)std::max<int64_t>(g->nnz, 1) * H, 4)) return 1;
         ghbuf = (float *)p;
     }
-    const int rc = amp::gno64_shape(H, Fi, Fo, d, 3) && g->n_rows > 0
+    const int rc = amp::gno64_shape(H, Fi, Fo, d, 3) && g->n_rows > 0 && amp::aligned16(x, grad)
                        ? amp::gno64_mlp_backward(g, d, theta, coords, x, grad, dtheta, ghbuf, px, px_half, cvec)
                        : mlp_backward_tiled(g, d, H, Fi, Fo, theta, coords, x, grad, dtheta, ghbuf);
     if (rc) return rc;
@@ -576,7 +576,7 @@ int athena_mp_gno_aggregate_fwd(const athena_mp_graph *g, int32_t d, int32_t H, 
     if (!gno_args_ok(g, d, H, Fi, Fo)) return 2;
     AMP_REQUIRE(theta && coords && x && m, "gno_aggregate_fwd: null pointer");
     const size_t off_V = (size_t)H * d + H;
-    if (gno64_shape(H, Fi, Fo, d, 4))
+    if (gno64_shape(H, Fi, Fo, d, 4) && aligned16(x, m, theta))   // (theta: gno_fused_kernel reads V 16 bytes per lane)
         return launch_gno_fused(g->rowptr, g->col, g->eid, x, coords, theta, d, theta + off_V, g->n_rows, &g->len_fwd, m, g->n_cols,
                                 g->n_edge_cols, g->nnz);
     // m[r,o] = sum_{(k,q)} S[r,(k,q)] Vaug[o + Fo*(q + Fi*k)]: B = theta+off_V viewed [R][Fo] row-major
@@ -599,6 +599,9 @@ int athena_mp_gno_aggregate_fwd_save(const athena_mp_graph *g, int32_t d, int32_
     AMP_REQUIRE(theta && coords && x && m && s_save, "gno_aggregate_fwd_save: null pointer");
     AMP_REQUIRE(gno64_saved_bytes(g, d, H, Fi, Fo) > 0,
                 "gno_aggregate_fwd_save: this shape does not keep S (athena_mp_gno_saved_bytes returned 0)");
+    // the one kernel that writes S moves x, m and S 16 bytes per lane, and S has no other producer
+    AMP_REQUIRE(aligned16(x, m, s_save), "gno_aggregate_fwd_save: x, m and s_save must be 16-byte aligned (athena_mp_gno_aggregate_fwd "
+                                         "takes any alignment)");
     const size_t off_V = (size_t)H * d + H;
     return launch_gno_fused(g->rowptr, g->col, g->eid, x, coords, theta, d, theta + off_V, g->n_rows, &g->len_fwd, m, g->n_cols,
                             g->n_edge_cols, g->nnz, s_save);
@@ -612,6 +615,8 @@ int athena_mp_gno_aggregate_bwd_theta_saved(const athena_mp_graph *g, int32_t d,
     AMP_REQUIRE(theta && coords && x && grad && s_save && dtheta, "gno_aggregate_bwd_theta_saved: null pointer");
     AMP_REQUIRE(gno64_saved_bytes(g, d, H, Fi, Fo) > 0,
                 "gno_aggregate_bwd_theta_saved: this shape does not keep S (athena_mp_gno_saved_bytes returned 0)");
+    if (!aligned16(x, grad, s_save))   // S is a function of x, coords and theta: the entry that rebuilds it takes any alignment
+        return athena_mp_gno_aggregate_bwd_theta(g, d, H, Fi, Fo, theta, coords, x, grad, dtheta);
     const size_t off_V = (size_t)H * d + H;
     const int rc = launch_gno_stg(g, x, coords, theta, d, grad, dtheta + off_V, s_save);
     if (rc) {
@@ -660,7 +665,7 @@ int athena_mp_gno_aggregate_bwd_theta(const athena_mp_graph *g, int32_t d, int32
     // contraction of tile t runs on the caller's.
     const int tile = tile_rows_for(g->n_rows, R);
     if (g->n_rows == 0) AMP_HIP(hipMemsetAsync(dtheta + off_V, 0, sizeof(float) * (size_t)R * Fo, stream()));
-    if (g->n_rows > 0 && gno64_shape(H, Fi, Fo, d, 3)) {   // S stays on chip (gno_stg_kernel)
+    if (g->n_rows > 0 && gno64_shape(H, Fi, Fo, d, 3) && aligned16(x, grad)) {   // S stays on chip (gno_stg_kernel)
         const int rc = launch_gno_stg(g, x, coords, theta, d, grad, dtheta + off_V);
         if (rc == 0) return gno_mlp_backward(g, d, H, Fi, Fo, theta, coords, x, grad, dtheta, nullptr);
         if (rc > 0) return rc;
@@ -721,6 +726,7 @@ int athena_mp_gno_aggregate_bwd(const athena_mp_graph *g, int32_t d, int32_t H, 
     if (fused) *fused = 0;
     bool ok = false;
     if (gno64_one_call_reverse(g, d, H, Fi, Fo, dx != nullptr, &ok)) return 1;
+    ok = ok && aligned16(x, grad, dx, s_save);   // the one-call kernels move all four 16 bytes per lane
     auto separate = [&]() -> int {   // the three entry points one after the other: no workspace of nnz * 256 bytes
         if (dtheta) {
             const int rc = s_save ? athena_mp_gno_aggregate_bwd_theta_saved(g, d, H, Fi, Fo, theta, coords, x, grad, s_save, dtheta)

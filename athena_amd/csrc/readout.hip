@@ -293,7 +293,7 @@ int athena_mp_duvenaud_readout_fwd(int64_t N, int32_t Fv, int32_t O, int32_t S, 
     AMP_REQUIRE(N >= 0 && Fv > 0 && O > 0 && S >= 0 && seg && R && out && (N == 0 || (z && p)),
                 "duvenaud_readout_fwd: bad arguments");
     if (N > 0) {
-        if (fused_readout_shape(Fv, O)) {
+        if (fused_readout_shape(Fv, O) && aligned16(z)) {   // z rows 16 bytes per lane
             const dim3 grid(readout_grid(N, 7));   // 66 VGPRs at Fv = 64: seven waves per SIMD
 #define AMP_CASE(J_)                                                                                               \
     if (Fv == 16 * J_) hipLaunchKernelGGL((readout_fwd_kernel<J_>), grid, dim3(256), 0, stream(), O, N, z, R, p);
@@ -328,7 +328,7 @@ int athena_mp_duvenaud_readout_bwd(int64_t N, int32_t Fv, int32_t O, int32_t S, 
         if (!accumulate) AMP_HIP(hipMemsetAsync(dR, 0, sizeof(float) * n, stream()));
         return 0;
     }
-    if (!fused_readout_shape(Fv, O)) {
+    if (!fused_readout_shape(Fv, O) || !aligned16(z, dz_next, dc)) {   // the fused kernel moves z, dz_next and dc 16 bytes per lane
         void *dl = nullptr;
         if (workspace(&dl, sizeof(float) * (size_t)N * O, 5)) return 1;
         int rc = athena_mp_softmax_segsum_bwd(O, N, S, seg, p, gout, (float *)dl);

@@ -22,6 +22,14 @@
  *     (default: the null stream) and return without synchronising.
  *   - not thread-safe by design (the reference's layers are stateful and
  *     single-threaded, SURVEY.md 8b "Threading").
+ *   - ALIGNMENT: every float * / int32_t * device argument needs only the natural alignment of its element type (4 bytes): a row
+ *     slice x(1, v0) of a larger array, an array carved out of one allocation at an odd element offset, are valid operands.
+ *     The fast routes are taken when the operands are 16-byte aligned (what athena_mp_malloc and every allocator return);
+ *     other calls take the entry's generic route and compute the same thing.  Two entries refuse instead, with a message
+ *     that says so, and say so where they are declared: athena_mp_device_copy (16-byte elements) and
+ *     athena_mp_gno_aggregate_fwd_save (S has one producer, which moves x, m and S 16 bytes at a time;
+ *     athena_mp_gno_aggregate_fwd takes any alignment).  An s_save_dev that is not 16-byte aligned is never read: the
+ *     reverse entries that take one rebuild S then.
  *   - ONE stream at a time per device: scratch workspaces (reduction slabs, the GNO partials, packed halo rows) belong
  *     to the device, not to a stream, and are ordered by the stream the calls are enqueued on.  Switching streams with
  *     athena_mp_set_stream is fine once the work enqueued so far on the old stream is ordered before the new stream's
@@ -426,7 +434,8 @@ int athena_mp_gno_aggregate_bwd_coords(const athena_mp_graph *g, int32_t d, int3
  * dVaug = S^T g streams it instead of rebuilding it.  Same m, same dtheta (bit for bit) as the pair above.
  *   _saved_bytes: *bytes = size of s_save_dev for this graph and shape, 0 if the shape does not take the
  *                 kernels that keep S (then use the pair above);
- *   _fwd_save:    athena_mp_gno_aggregate_fwd that also fills s_save_dev;
+ *   _fwd_save:    athena_mp_gno_aggregate_fwd that also fills s_save_dev; x_dev, m_dev and s_save_dev must be 16-byte aligned
+ *                 (refused otherwise, the outputs untouched: athena_mp_gno_aggregate_fwd takes any alignment);
  *   _bwd_theta_saved: athena_mp_gno_aggregate_bwd_theta reading the s_save_dev of the SAME graph, theta, coords, x. */
 int athena_mp_gno_saved_bytes(const athena_mp_graph *g, int32_t d, int32_t H, int32_t Fi, int32_t Fo,
                               int64_t *bytes);

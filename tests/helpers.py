@@ -96,3 +96,72 @@ def elementwise_worst(a, b, scale):
     what was added, not to its tiny value, and no element hides behind the tensor's maximum"""
     a, b, scale = (np.asarray(t, np.float64) for t in (a, b, scale))
     return float((np.abs(a - b) / np.maximum(scale, 1e-30)).max()) if a.size else 0.0
+
+
+# ---- operands at chosen alignments, between guards (tests/test_gpu_unaligned.py) ---------------------------------------------------
+# A torch allocation starts on a 256-byte boundary and is rounded up to 512 bytes, so a fresh tensor never shows what a kernel does
+# with a pointer that is only 4- or 8-byte aligned, nor a store a few elements past the end.  placed / placed_out put an operand k
+# elements past a 512-byte boundary inside a larger buffer filled with a sentinel:
+#   k = 1   4-byte aligned
+#   k = 2   8-byte aligned
+#   k = 4   16-byte aligned, but 16 bytes off every 32-byte (and 256-, 512-byte) boundary, flush against its guards
+SENTINEL = {"float32": 0x7FC0ABCD, "int32": 0x5A5A5A5A}   # a quiet NaN with a payload / a pattern no index or count takes
+
+
+def _placed_raw(n, dtype, dev, k, guard):
+    """(raw int32 buffer filled with the sentinel of dtype, index of the operand's first element)"""
+    import torch
+
+    name = str(dtype).replace("torch.", "")
+    assert name in SENTINEL and k >= 0 and guard >= 0
+    lead = 128 * ((guard + 127) // 128)                    # whole 512-byte blocks that hold the front guard
+    raw = torch.full((127 + lead + k + n + guard,), SENTINEL[name], dtype=torch.int32, device=dev)
+    assert raw.data_ptr() % 4 == 0
+    first = (-(raw.data_ptr() // 4)) % 128                 # elements up to the next 512-byte boundary, whatever the allocator returned
+    return raw, first + lead + k
+
+
+def placed(array, dev, k, guard=256):
+    """`array` (numpy float32 / int32) on the device, its first element k elements past a 512-byte boundary, `guard` sentinel
+    elements on both sides; returns the contiguous view"""
+    import torch
+
+    a = np.ascontiguousarray(array)
+    t = torch.from_numpy(a)
+    raw, s = _placed_raw(a.size, t.dtype, dev, k, guard)
+    view = raw[s:s + a.size].view(t.dtype).reshape(a.shape)
+    view.copy_(t)
+    assert view.is_contiguous() and view.data_ptr() % 16 == (4 * k) % 16 and (view.data_ptr() - 4 * k) % 512 == 0
+    return view
+
+
+def placed_out(shape, dtype, dev, k, guard=256, init=None):
+    """an output of this shape placed like `placed`, pre-filled with the sentinel (init: the contents of an in-place operand
+    instead); returns (view, check): check() asserts, word for word, that no guard element on either side was written"""
+    import torch
+
+    n = int(np.prod(shape))
+    raw, s = _placed_raw(n, dtype, dev, k, guard)
+    view = raw[s:s + n].view(dtype).reshape(tuple(shape))
+    if init is not None:
+        view.copy_(torch.from_numpy(np.ascontiguousarray(init)))
+    assert view.is_contiguous() and view.data_ptr() % 16 == (4 * k) % 16 and (view.data_ptr() - 4 * k) % 512 == 0
+    word = SENTINEL[str(dtype).replace("torch.", "")]
+
+    def check(what=""):
+        torch.cuda.synchronize()
+        front, back = raw[s - guard:s], raw[s + n:s + n + guard]
+        for side, part in (("before", front), ("after", back)):
+            bad = torch.nonzero(part != word).flatten()
+            assert bad.numel() == 0, (f"{what}: {bad.numel()} guard word(s) {side} the output overwritten, the first at element "
+                                      f"{int(bad[0]) - (guard if side == 'before' else 0)} relative to that end")
+
+    return view, check
+
+
+def unwritten(view):
+    """number of elements of an output from placed_out that still hold the sentinel (compared as words: a NaN equals nothing)"""
+    import torch
+
+    word = SENTINEL[str(view.dtype).replace("torch.", "")]
+    return int((view.reshape(-1).view(torch.int32) == word).sum())
