@@ -6,5 +6,7 @@ C ABI (include/athena_mp.h), plus the host-side mirrors of the reference interfa
 """
 from . import _capi  # noqa: F401
 from .graph import DeviceGraph, graph_type  # noqa: F401
+from . import geometry  # noqa: F401
+from .geometry import points_grad, structures_grad, structures_grad_host  # noqa: F401
 
-__all__ = ["_capi", "DeviceGraph", "graph_type"]
+__all__ = ["_capi", "DeviceGraph", "graph_type", "geometry", "points_grad", "structures_grad", "structures_grad_host"]

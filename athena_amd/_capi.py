@@ -45,6 +45,10 @@ _PROTOS = {
     "athena_mp_periodic_pairs": [_i32, _i32, _vp, _vp, _vp, _vp, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp],
     "athena_mp_periodic_graph_host": [_i32, _i32, _vp, _vp, _vp, _vp, _f32, _f32, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp,
                                       _vp],
+    "athena_mp_edge_grad_to_points": [_vp, _i32, _vp, _vp],
+    "athena_mp_periodic_grad": [_vp, _i32, _i32, _vp, _vp, _vp, _f32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp],
+    "athena_mp_edge_grad_to_points_host": [_vp, _i32, _vp, _vp],
+    "athena_mp_periodic_grad_host": [_vp, _i32, _i32, _vp, _vp, _vp, _f32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp],
     "athena_mp_graph_export": [_vp, _i32, _vp, _i64, _vp],
     "athena_mp_graph_destroy": [_vp],
     "athena_mp_graph_key": [_i32, _i64, _vp, _vp, C.POINTER(C.c_uint64)],

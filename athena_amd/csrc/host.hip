@@ -650,6 +650,33 @@ int athena_mp_gno_aggregate_bwd_coords_host(const athena_mp_graph *g, int32_t d,
                   });
 }
 
+// ---- geometry gradients (geometry_grad.hip): checked first, so no array is read at a length the arguments do not agree on --------
+int athena_mp_edge_grad_to_points_host(const athena_mp_graph *g, int32_t dim, const float *dcoords, float *dpoints)
+{
+    if (int rc = points_grad_check(g, dim)) return rc;
+    AMP_REQUIRE((g->n_edge_cols == 0 || dcoords) && (g->n_rows == 0 || dpoints), "edge_grad_to_points_host: null array");
+    return staged({{dcoords, nullptr, fb(g->n_edge_cols, dim)}, {nullptr, dpoints, fb(g->n_rows, dim), true}},
+                  [&](std::vector<void *> &p) { return athena_mp_edge_grad_to_points(g, dim, (float *)p[0], (float *)p[1]); });
+}
+int athena_mp_periodic_grad_host(const athena_mp_graph *g, int32_t B, int32_t n, const int32_t *offsets, const int64_t *edge_offsets,
+                                 const float *lat, float cutoff_max, const float *vec, const float *dfeature, int32_t fe_cols,
+                                 const float *dvec, float *dcart, float *dfrac, float *virial, float *dlat)
+{
+    if (int rc = periodic_grad_check(g, B, n, offsets, edge_offsets, cutoff_max, dfeature != nullptr, fe_cols, dvec != nullptr)) return rc;
+    const int64_t E = g->n_edge_cols;
+    AMP_REQUIRE((E == 0 || vec) && (B == 0 || lat), "periodic_grad_host: null array");
+    // an absent operand is staged as nothing and handed on as NULL
+    auto in = [](const float *h, size_t bytes) { return Stage{h, nullptr, h ? bytes : 0}; };
+    auto out = [](float *h, size_t bytes) { return Stage{nullptr, h, h ? bytes : 0, true}; };
+    return staged({in(lat, fb(B, 9)), in(vec, fb(E, 3)), in(dfeature, fb(E, fe_cols)), in(dvec, fb(E, 3)), out(dcart, fb(n, 3)),
+                   out(dfrac, fb(n, 3)), out(virial, fb(B, 9)), out(dlat, fb(B, 9))},
+                  [&](std::vector<void *> &p) {
+                      auto dev = [&](int k, const void *h) { return h ? (float *)p[k] : (float *)nullptr; };
+                      return athena_mp_periodic_grad(g, B, n, offsets, edge_offsets, dev(0, lat), cutoff_max, dev(1, vec), dev(2, dfeature),
+                                                     fe_cols, dev(3, dvec), dev(4, dcart), dev(5, dfrac), dev(6, virial), dev(7, dlat));
+                  });
+}
+
 
 // ---- composites and shaped activations ---------------------------------------------------------------
 int athena_mp_duvenaud_update_act_fwd_host(const athena_mp_graph *g, int32_t Fi, int32_t Fo, int32_t mn, int32_t mx,

@@ -52,6 +52,8 @@ module athena_mp_c
   public :: athena_mp_csr_from_edges, athena_mp_graph_export, athena_mp_graph_create_from_edges
   public :: athena_mp_graph_create_from_edges_dev, athena_mp_radius_pairs, athena_mp_radius_graph_host
   public :: athena_mp_periodic_pairs, athena_mp_periodic_graph_host
+  public :: athena_mp_edge_grad_to_points, athena_mp_periodic_grad
+  public :: athena_mp_edge_grad_to_points_host, athena_mp_periodic_grad_host
   public :: athena_mp_error_message
   public :: athena_mp_pull_gemm, athena_mp_dev_offset, athena_mp_kipf_layer_bwd
   public :: athena_mp_comm_create, athena_mp_comm_create_from_file, athena_mp_comm_destroy, athena_mp_comm_barrier
@@ -538,6 +540,48 @@ module athena_mp_c
        type(c_ptr), value :: adj_ia, adj_ja, feature, vec, first_count, edge_offsets
        integer(c_int64_t), value :: capacity, edge_capacity
        integer(c_int64_t), intent(out) :: nnz, n_pairs
+     end function
+     !! geometry gradients, the reverse step of the two builders (definition: include/athena_mp.h).  The reverse of
+     !! athena_mp_radius_pairs: dcoords (dim, E) on the device -> dpoints (dim, n) on the device, a signed sum over the handle's rows
+     integer(c_int) function athena_mp_edge_grad_to_points(graph, dim, dcoords_dev, dpoints_dev) &
+          bind(C, name="athena_mp_edge_grad_to_points")
+       import :: c_int, c_int32_t, c_ptr
+       type(c_ptr), value :: graph, dcoords_dev, dpoints_dev
+       integer(c_int32_t), value :: dim
+     end function
+     !! the reverse of athena_mp_periodic_pairs: offsets and edge_offsets (n_structures + 1) on the host; lat (3, 3, n_structures),
+     !! vec (3, E), dfeature (fe_cols, E), dvec (3, E) on the device (one of the last two may be c_null_ptr) -> dcart (3, n_atoms),
+     !! dfrac (3, n_atoms), virial (3, 3, n_structures), dlat (3, 3, n_structures) on the device, each may be c_null_ptr.
+     !! virial(d, c, s) = sum x_c gx_d and dlat(d, a, s) = dE/dL[a][d]: the row-major [B, 3, 3] arrays of the C side
+     integer(c_int) function athena_mp_periodic_grad(graph, n_structures, n_atoms, offsets, edge_offsets, lat_dev, cutoff_max, &
+          vec_dev, dfeature_dev, fe_cols, dvec_dev, dcart_dev, dfrac_dev, virial_dev, dlat_dev) &
+          bind(C, name="athena_mp_periodic_grad")
+       import :: c_int, c_int32_t, c_int64_t, c_float, c_ptr
+       type(c_ptr), value :: graph, lat_dev, vec_dev, dfeature_dev, dvec_dev, dcart_dev, dfrac_dev, virial_dev, dlat_dev
+       integer(c_int32_t), value :: n_structures, n_atoms, fe_cols
+       integer(c_int32_t), intent(in) :: offsets(*)
+       integer(c_int64_t), intent(in) :: edge_offsets(*)
+       real(c_float), value :: cutoff_max
+     end function
+     !! the same two with host arrays (staged): dcoords (dim, E) -> dpoints (dim, n)
+     integer(c_int) function athena_mp_edge_grad_to_points_host(graph, dim, dcoords, dpoints) &
+          bind(C, name="athena_mp_edge_grad_to_points_host")
+       import :: c_int, c_int32_t, c_float, c_ptr
+       type(c_ptr), value :: graph
+       integer(c_int32_t), value :: dim
+       real(c_float), intent(in) :: dcoords(dim, *)
+       real(c_float), intent(inout) :: dpoints(dim, *)
+     end function
+     !! ... dfeature, dvec and the four outputs passed as c_loc of host arrays, or c_null_ptr
+     integer(c_int) function athena_mp_periodic_grad_host(graph, n_structures, n_atoms, offsets, edge_offsets, lat, cutoff_max, &
+          vec, dfeature, fe_cols, dvec, dcart, dfrac, virial, dlat) bind(C, name="athena_mp_periodic_grad_host")
+       import :: c_int, c_int32_t, c_int64_t, c_float, c_ptr
+       type(c_ptr), value :: graph, dfeature, dvec, dcart, dfrac, virial, dlat
+       integer(c_int32_t), value :: n_structures, n_atoms, fe_cols
+       integer(c_int32_t), intent(in) :: offsets(*)
+       integer(c_int64_t), intent(in) :: edge_offsets(*)
+       real(c_float), intent(in) :: lat(3, 3, *), vec(3, *)
+       real(c_float), value :: cutoff_max
      end function
      !! one array of the handle back on the host (which: see include/athena_mp.h); host_dst = c_null_ptr queries count
      integer(c_int) function athena_mp_graph_export(graph, which, host_dst, capacity, count) &

@@ -1,0 +1,136 @@
+"""Geometry gradients: a layer's per-edge gradient carried back to the points, the atoms and the cell, on the device
+(athena_amd/csrc/geometry_grad.hip; the definition, term by term in fp32, is in include/athena_mp.h).
+
+    handle, coords = DeviceGraph.from_points(points, radius)            # coords[e] = p_i - p_j
+    ... graph_nop_layer_type.backward(need_coord_grad=True) -> dcoords [E, d]
+    dpoints = points_grad(handle, dcoords)                              # [n, d]
+
+    handle, feature, vec, voff, eoff = DeviceGraph.from_structures(frac, lat, offsets, cutoff_min, cutoff_max)
+    ... duvenaud_msgpass_layer_type.backward(need_edge_grad=True) -> de [E, F_e]
+    g = structures_grad(handle, lat, voff, eoff, vec, cutoff_max, dfeature=de)
+    forces = -g["cart"];  g["frac"], g["virial"], g["lat"]
+
+There is no autograd wrapper: these are the reverse steps themselves, to be called where the chain needs them."""
+import ctypes as C
+
+import numpy as np
+
+from . import _capi
+
+WANT = ("cart", "frac", "virial", "lat")
+
+
+def points_grad(handle, dcoords, out=None):
+    """The reverse of DeviceGraph.from_points (athena_mp_edge_grad_to_points): dcoords [E, dim] float32 on the device, the gradient
+    with respect to coords[e] = p_i - p_j -> dpoints [n, dim], the gradient with respect to the points.  Row i is the signed sum
+    over the handle's row i in CSR order (+ where i is the smaller index of the edge, - where it is the larger); bit for bit the
+    sequential sum.  out: a contiguous float32 device tensor [n, dim] to write into."""
+    import torch
+
+    if not (isinstance(dcoords, torch.Tensor) and dcoords.is_cuda and dcoords.dtype == torch.float32 and dcoords.dim() == 2
+            and dcoords.is_contiguous()):
+        raise ValueError("dcoords must be a contiguous float32 device tensor [E, dim]")
+    E, dim = int(dcoords.shape[0]), int(dcoords.shape[1])
+    if E != handle.n_edge_cols:
+        raise ValueError(f"dcoords holds {E} rows, the handle has {handle.n_edge_cols} edge columns")
+    n = handle.n_rows
+    if out is None:
+        out = torch.empty((n, dim), dtype=torch.float32, device=dcoords.device)
+    elif not (out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (n, dim) and out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous float32 device tensor [{n}, {dim}]")
+    _capi.use_torch_stream()
+    _capi.call("athena_mp_edge_grad_to_points", handle.handle, dim, C.c_void_p(dcoords.data_ptr()), C.c_void_p(out.data_ptr()))
+    return out
+
+
+def _host_tables(handle, lat_rows, offsets, edge_offsets, want):
+    off = np.ascontiguousarray(offsets, dtype=np.int32)
+    eoff = np.ascontiguousarray(edge_offsets, dtype=np.int64)
+    if not (off.ndim == 1 and off.size >= 1 and eoff.shape == off.shape and lat_rows == off.size - 1):
+        raise ValueError("offsets and edge_offsets must be [B + 1] with lat [B, 3, 3]")
+    want = tuple(want)
+    if not want or any(w not in WANT for w in want):
+        raise ValueError(f"want must name some of {WANT}")
+    return off, eoff, want
+
+
+def structures_grad(handle, lat, offsets, edge_offsets, vec, cutoff_max, dfeature=None, dvec=None, want=WANT, out=None):
+    """The reverse of DeviceGraph.from_structures (athena_mp_periodic_grad).  handle, vec [E, 3], offsets (vertex_offsets) and
+    edge_offsets as from_structures returned them, lat [B, 3, 3] and cutoff_max as it took them; dfeature [E, fe_cols] (the de of a
+    layer whose edge input was `feature` in every column) and / or dvec [E, 3]: float32 device tensors.  Returns a dict of device
+    tensors for the names in `want`: "cart" [n, 3] = dE/d(Cartesian position) (forces are its negative), "frac" [n, 3],
+    "virial" [B, 3, 3] = sum over a structure's edges of vec (x) gx, "lat" [B, 3, 3] = L^-T virial = dE/dL at fixed fractional
+    coordinates.  out: a dict of contiguous float32 device tensors to write into, by the same names."""
+    import torch
+
+    dev = vec.device if isinstance(vec, torch.Tensor) else torch.device("cuda", 0)
+    f32 = lambda t, what: _f32_device(t, dev, what)
+    lat = f32(lat, "lat")
+    vec = f32(vec, "vec")
+    off, eoff, want = _host_tables(handle, int(lat.shape[0]), offsets, edge_offsets, want)
+    B, n, E = off.size - 1, int(off[-1]), int(vec.shape[0])
+    if not (tuple(lat.shape[1:]) == (3, 3) and tuple(vec.shape) == (E, 3)):
+        raise ValueError("lat must be [B, 3, 3] and vec [E, 3]")
+    fe_cols = 0
+    if dfeature is not None:
+        dfeature = f32(dfeature, "dfeature")
+        if dfeature.dim() == 1:
+            dfeature = dfeature[:, None]
+        if not (dfeature.dim() == 2 and dfeature.shape[0] == E):
+            raise ValueError("dfeature must be [E, fe_cols]")
+        fe_cols = int(dfeature.shape[1])
+    if dvec is not None:
+        dvec = f32(dvec, "dvec")
+        if tuple(dvec.shape) != (E, 3):
+            raise ValueError("dvec must be [E, 3]")
+    shapes = {"cart": (n, 3), "frac": (n, 3), "virial": (B, 3, 3), "lat": (B, 3, 3)}
+    res = {}
+    for w in want:
+        t = None if out is None else out.get(w)
+        if t is None:
+            t = torch.empty(shapes[w], dtype=torch.float32, device=dev)
+        elif not (t.is_cuda and t.dtype == torch.float32 and tuple(t.shape) == shapes[w] and t.is_contiguous()):
+            raise ValueError(f"out[{w!r}] must be a contiguous float32 device tensor {shapes[w]}")
+        res[w] = t
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    _capi.use_torch_stream()
+    _capi.call("athena_mp_periodic_grad", handle.handle, B, n, vp(off), vp(eoff), ptr(lat), float(cutoff_max), ptr(vec), ptr(dfeature),
+               fe_cols, ptr(dvec), ptr(res.get("cart")), ptr(res.get("frac")), ptr(res.get("virial")), ptr(res.get("lat")))
+    return res
+
+
+def _f32_device(t, dev, what):
+    """a contiguous float32 device tensor as it is (no copy: its address is the caller's), a numpy array uploaded"""
+    import torch
+
+    if isinstance(t, torch.Tensor):
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+            raise ValueError(f"{what} must be a contiguous float32 device tensor (or a numpy array)")
+        return t
+    return torch.from_numpy(np.ascontiguousarray(t, dtype=np.float32)).to(dev)
+
+
+def structures_grad_host(handle, lat, offsets, edge_offsets, vec, cutoff_max, dfeature=None, dvec=None, want=WANT):
+    """structures_grad for numpy arrays (athena_mp_periodic_grad_host: every array staged through HBM, what a caller that holds
+    Fortran arrays uses); returns a dict of numpy arrays"""
+    lat = np.ascontiguousarray(lat, dtype=np.float32).reshape(-1, 3, 3)
+    vec = np.ascontiguousarray(vec, dtype=np.float32).reshape(-1, 3)
+    off, eoff, want = _host_tables(handle, lat.shape[0], offsets, edge_offsets, want)
+    B, n, E = off.size - 1, int(off[-1]), vec.shape[0]
+    fe_cols = 0
+    if dfeature is not None:
+        dfeature = np.ascontiguousarray(dfeature, dtype=np.float32)
+        if dfeature.ndim == 1:
+            dfeature = dfeature[:, None]
+        if not (dfeature.ndim == 2 and dfeature.shape[0] == E):
+            raise ValueError("dfeature must be [E, fe_cols]")
+        fe_cols = dfeature.shape[1]
+    if dvec is not None:
+        dvec = np.ascontiguousarray(dvec, dtype=np.float32).reshape(E, 3)
+    shapes = {"cart": (n, 3), "frac": (n, 3), "virial": (B, 3, 3), "lat": (B, 3, 3)}
+    res = {w: np.empty(shapes[w], np.float32) for w in want}
+    vp = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+    _capi.call("athena_mp_periodic_grad_host", handle.handle, B, n, vp(off), vp(eoff), vp(lat), float(cutoff_max), vp(vec), vp(dfeature),
+               fe_cols, vp(dvec), vp(res.get("cart")), vp(res.get("frac")), vp(res.get("virial")), vp(res.get("lat")))
+    return res

@@ -174,6 +174,47 @@ int athena_mp_periodic_graph_host(int32_t n_structures, int32_t n_atoms, const i
                                   int32_t add_self_loops, int32_t *adj_ia_out, int32_t *adj_ja_out, int64_t capacity,
                                   int64_t *nnz_out, float *feature_out, float *vec_out, int32_t *first_count_out,
                                   int64_t edge_capacity, int64_t *n_pairs_out, int64_t *edge_offsets_out);
+/* Geometry gradients (geometry_grad.hip): the reverse step of the two builders above.  The layers return their gradient per edge,
+ * in HBM (athena_mp_gno_aggregate_bwd_coords: dcoords [E, d]; athena_mp_duvenaud_propagate_bwd_e: de [E, F_e]); these entries carry
+ * it back to the points, the atoms and the cell.  Nothing in the reference corresponds to them (its edge geometry carries no
+ * gradient).  g is the handle built from the builder's pair list with edge ids (athena_mp_graph_create_from_edges_dev,
+ * with_edge_ids = 1), add_self_loops or not.
+ * Definition.  All arithmetic is fp32, every operation rounded on its own, / and sqrt correctly rounded, as the builders.  Row i of
+ * the handle is its forward CSR as athena_mp_graph_export shows it (rowptr, col, eid, 0-based, eid = -1: none); that order is the
+ * summation order.
+ *   Signed gather: acc = +0; for k = rowptr[i] .. rowptr[i+1]-1 in order, c = col[k], e = eid[k]: the entry is skipped when e < 0 (a
+ *   self loop) or c == i (a self-image edge: its two ends are the same atom); else acc = acc + t_e when i < c, acc = acc - t_e when
+ *   i > c.  out[i] = acc.  A row without entries gives +0; every output element is written.
+ *   Points mode, the reverse of athena_mp_radius_pairs: t_e = dcoords[e, :] (dim in 1..3), dpoints [n, dim] = out.
+ *   Periodic mode, the reverse of athena_mp_periodic_pairs: lat [B, 3, 3], cutoff_max and vec [E, 3] as the builder took and wrote
+ *   them, offsets [B + 1] (int32) and edge_offsets [B + 1] (int64) on the HOST; dfeature [E, fe_cols] (fe_cols >= 1: the de of a
+ *   layer whose edge input was `feature` in every column) and dvec [E, 3], each may be NULL, not both.  Per edge, x = vec[e]:
+ *     s = ((x0 * x0) + x1 * x1) + x2 * x2, r = sqrt(s)  (the builder's own s and r; r > cutoff_min >= 0)
+ *     q = (((de[e,0] + de[e,1]) + ...) + de[e,fe_cols-1]) / cutoff_max;  u_c = x_c / r
+ *     gx_c = dvec[e,c] + q * u_c  (q * u_c alone when dvec is NULL, dvec[e,c] alone when dfeature is NULL)
+ *   Outputs in HBM, each may be NULL:
+ *     dcart [n, 3]      the signed gather of t_e = gx_e: dE/d(Cartesian position); forces are its negative
+ *     dfrac [n, 3]      dfrac[i,k] = ((L[k][0] * g0) + L[k][1] * g1) + L[k][2] * g2, g = dcart[i], L the lattice of i's structure (on
+ *                       open axes too)
+ *     virial [B, 3, 3]  virial[s][c][d] = sum over e in [edge_offsets[s], edge_offsets[s+1]) of x_c * gx_d.  The summation order is
+ *                       free; no atomics: two runs are byte-identical.  Not symmetric when dvec is given; an empty structure gives 0.
+ *     dlat [B, 3, 3]    L^-T * virial: dE/dL at fixed fractional coordinates (x = v L), formed per structure in fp64 from the fp32
+ *                       lattice and the fp32 virial, rounded once
+ * Refused with a message: a handle without edge columns, n_atoms != the handle's rows, edge_offsets[B] != the handle's edge columns,
+ * offsets / edge_offsets not ascending from 0, dim outside 1..3, fe_cols < 1 with dfeature, both gradients NULL, cutoff_max not
+ * finite or <= 0, dlat asked for with det L zero or not finite (the structure is named; virial alone never needs the inverse).
+ * n = 0 or E = 0 succeeds (with E = 0 every per-edge array is empty and may be NULL).  The values of the gradients are not scanned: NaN propagates. */
+int athena_mp_edge_grad_to_points(const athena_mp_graph *g, int32_t dim, const float *dcoords_dev, float *dpoints_dev);
+int athena_mp_periodic_grad(const athena_mp_graph *g, int32_t n_structures, int32_t n_atoms, const int32_t *offsets_host,
+                            const int64_t *edge_offsets_host, const float *lat_dev, float cutoff_max, const float *vec_dev,
+                            const float *dfeature_dev, int32_t fe_cols, const float *dvec_dev, float *dcart_dev, float *dfrac_dev,
+                            float *virial_dev, float *dlat_dev);
+/* The same two with every array on the host (a handle plus Fortran arrays), staged through HBM */
+int athena_mp_edge_grad_to_points_host(const athena_mp_graph *g, int32_t dim, const float *dcoords, float *dpoints);
+int athena_mp_periodic_grad_host(const athena_mp_graph *g, int32_t n_structures, int32_t n_atoms, const int32_t *offsets,
+                                 const int64_t *edge_offsets, const float *lat, float cutoff_max, const float *vec,
+                                 const float *dfeature, int32_t fe_cols, const float *dvec, float *dcart, float *dfrac, float *virial,
+                                 float *dlat);
 int athena_mp_graph_export(const athena_mp_graph *g, int32_t which, void *host_dst, int64_t capacity,
                            int64_t *count);
 int athena_mp_graph_destroy(athena_mp_graph *g);
