@@ -8,5 +8,7 @@ from . import _capi  # noqa: F401
 from .graph import DeviceGraph, graph_type  # noqa: F401
 from . import geometry  # noqa: F401
 from .geometry import points_grad, structures_grad, structures_grad_host  # noqa: F401
+from . import batching  # noqa: F401
+from .batching import Batch, DeviceDataset  # noqa: F401
 
-__all__ = ["_capi", "DeviceGraph", "graph_type", "geometry", "points_grad", "structures_grad", "structures_grad_host"]
+__all__ = ["_capi", "DeviceGraph", "graph_type", "geometry", "points_grad", "structures_grad", "structures_grad_host", "batching", "Batch", "DeviceDataset"]

@@ -54,6 +54,7 @@ module athena_mp_c
   public :: athena_mp_periodic_pairs, athena_mp_periodic_graph_host
   public :: athena_mp_edge_grad_to_points, athena_mp_periodic_grad
   public :: athena_mp_edge_grad_to_points_host, athena_mp_periodic_grad_host
+  public :: athena_mp_batch_plan_create, athena_mp_batch_plan_destroy, athena_mp_batch_select
   public :: athena_mp_error_message
   public :: athena_mp_pull_gemm, athena_mp_dev_offset, athena_mp_kipf_layer_bwd
   public :: athena_mp_comm_create, athena_mp_comm_create_from_file, athena_mp_comm_destroy, athena_mp_comm_barrier
@@ -582,6 +583,30 @@ module athena_mp_c
        integer(c_int64_t), intent(in) :: edge_offsets(*)
        real(c_float), intent(in) :: lat(3, 3, *), vec(3, *)
        real(c_float), value :: cutoff_max
+     end function
+     !! mini-batches out of a dataset handle that stays on the device (definition: include/athena_mp.h).  The plan: offsets and
+     !! edge_offsets (n_structures + 1) on the host, 0-based; edge_offsets = c_null_ptr for a handle without edge columns
+     integer(c_int) function athena_mp_batch_plan_create(graph, n_structures, offsets, edge_offsets, plan) &
+          bind(C, name="athena_mp_batch_plan_create")
+       import :: c_int, c_int32_t, c_ptr
+       type(c_ptr), value :: graph, edge_offsets
+       integer(c_int32_t), value :: n_structures
+       integer(c_int32_t), intent(in) :: offsets(*)
+       type(c_ptr), intent(out) :: plan
+     end function
+     integer(c_int) function athena_mp_batch_plan_destroy(plan) bind(C, name="athena_mp_batch_plan_destroy")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: plan
+     end function
+     !! sel (n_sel) 0-based structure ids on the host -> the child handle; offsets_out (n_sel + 1, int32) and edge_offsets_out
+     !! (n_sel + 1, int64) as c_loc of host arrays, vertex_map_dev / edge_map_dev device pointers: each may be c_null_ptr.
+     !! child = c_loc of a type(c_ptr), target variable that receives the handle; child = c_null_ptr is the size query
+     integer(c_int) function athena_mp_batch_select(plan, n_sel, sel, child, offsets_out, edge_offsets_out, vertex_map_dev, &
+          edge_map_dev) bind(C, name="athena_mp_batch_select")
+       import :: c_int, c_int32_t, c_ptr
+       type(c_ptr), value :: plan, child, offsets_out, edge_offsets_out, vertex_map_dev, edge_map_dev
+       integer(c_int32_t), value :: n_sel
+       integer(c_int32_t), intent(in) :: sel(*)
      end function
      !! one array of the handle back on the host (which: see include/athena_mp.h); host_dst = c_null_ptr queries count
      integer(c_int) function athena_mp_graph_export(graph, which, host_dst, capacity, count) &

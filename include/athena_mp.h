@@ -250,6 +250,47 @@ int athena_mp_graph_evict(athena_mp_graph *g);
 /* cached handles alive or idle, lookups served from the cache, and device graph handles BUILT by this process so far
  * (graph_create / _from_edges / _acquire misses / shard blocks): what the cache tests count */
 int athena_mp_graph_cache_stats(int64_t *handles, int64_t *hits, int64_t *builds);
+/* Mini-batches out of a dataset handle that stays in HBM (batch_select.hip): what network%train does with get_sample(input_graph,
+ * i0, i1) under shuffle_batches, without assembling the batch on the host or searching its neighbours again.  A plan
+ * is made once per dataset handle; a select turns a list of structure ids into a new, independent handle plus index maps.
+ * Parent: a handle g with n_rows == n_cols whose degrees are its row lengths (not a shard block built with row_deg / col_deg);
+ *   offsets [B + 1] int32 on the HOST, 0-based, ascending from 0 to n_rows (empty structures allowed); edge_offsets [B + 1] int64 on
+ *   the HOST, ascending from 0 to n_edge_cols, NULL exactly when the handle has no edge columns (a Kipf handle; an all-zero array is
+ *   taken as NULL there).
+ * Block-diagonal condition: every entry k of the rows [offsets[s], offsets[s+1]) has col[k] in that same range and eid[k] == -1 or
+ *   eid[k] in [edge_offsets[s], edge_offsets[s+1]).  Every handle of DeviceGraph.from_structures, of a layer's batched set_graph and
+ *   of io.batch_graphs satisfies it.  The transposed CSR and the edge-column index are then cut at the same places.
+ * Child, for sel[0..m) (0-based structure ids, repeats allowed, any order): with nv[s], ne[s], nw[s] a structure's vertex, edge-column
+ *   and entry counts and cv[t], ce[t], cw[t] their exclusive prefix sums over the selection, child row cv[t] + i is parent row
+ *   offsets[s] + i, s = sel[t], entries in the same order:
+ *     col' = col - offsets[s] + cv[t];  eid' = eid < 0 ? -1 : eid - edge_offsets[s] + ce[t];  coef' = coef bit for bit (degrees are row
+ *     lengths and do not change);  t_rowptr, t_src (a vertex rebase), t_eid, t_coef likewise;  e_rowptr, e_row (a vertex rebase) and
+ *     e_entry (an entry rebase: w - rowptr[offsets[s]] + cw[t]) cut at the edge-column boundaries;  deg_row, deg_col copied.
+ *     max_row_len, max_col_len: the maximum over the selected structures;  band: the maximum over the selected structures of each
+ *     structure's own max |col - row|, INT32_MAX (unknown) above 64, as graph_create;  the long-row plans are rebuilt for the child.
+ *   The child is, array for array, the handle athena_mp_graph_create_from_edges builds from the child's own pair list (the selected
+ *   structures' pairs in selection order, renumbered, with the parent's add_self_loops and with_edge_ids).  It is a deep copy, never in
+ *   the handle cache, freed by athena_mp_graph_destroy, and stays valid after the plan and the parent are gone.  The plan needs the
+ *   parent alive.  Note: a child always carries a band; a parent built on the device without its adjacency does not (graph_create
+ *   computes the band from adj_ja on the host), so a child may take the banded gathers where its parent does not.
+ * athena_mp_batch_select: offsets_out [m + 1] (int32) = cv with the child's vertex count last, edge_offsets_out [m + 1] (int64) = ce,
+ *   both on the host, each may be NULL.  out == NULL: size query, only the two host arrays are filled and the device is not touched.
+ *   vertex_map_dev [n_child]: vertex_map[cv[t] + i] = offsets[s] + i;  edge_map_dev [ne_child]: edge_map[ce[t] + j] = edge_offsets[s]
+ *   + j (int32, 0-based, in HBM; each may be NULL): the rows of the dataset's per-vertex / per-edge tensors the batch uses
+ *   (athena_mp_gather_rows).  The plan holds every per-structure table, so a select computes all sizes on the host and needs no
+ *   device -> host copy and no synchronise: one upload of the selection's table, one launch (on the library's stream) for the
+ *   thirteen arrays and both maps, no atomics; two selects of the same ids are byte-identical.  (It waits only for the stream to have
+ *   taken the PREVIOUS select's table out of the plan's pinned staging block.)
+ * Refused with a message, which names the structure or the id where there is one: a null argument, a rectangular handle or one with
+ * explicit degrees, offsets / edge_offsets not ascending from 0 to the handle's rows / edge columns, edge_offsets given for a handle
+ * without edge columns or missing for one with them, an entry that leaves its structure (found by the plan's check kernel, read as a
+ * flag by the host), n_sel < 1, an id outside [0, B), a child of 2^31 entries or more. */
+typedef struct athena_mp_batch_plan athena_mp_batch_plan;
+int athena_mp_batch_plan_create(const athena_mp_graph *g, int32_t n_structures, const int32_t *offsets_host,
+                                const int64_t *edge_offsets_host, athena_mp_batch_plan **out);
+int athena_mp_batch_plan_destroy(athena_mp_batch_plan *p);
+int athena_mp_batch_select(const athena_mp_batch_plan *p, int32_t n_sel, const int32_t *sel_host, athena_mp_graph **out,
+                           int32_t *offsets_out, int64_t *edge_offsets_out, int32_t *vertex_map_dev, int32_t *edge_map_dev);
 
 /* ---- Kipf --------------------------------------------------------------- */
 /* kipf_propagate, athena_diffstruc_extd_sub_kipf.f90:7-59
