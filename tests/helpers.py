@@ -98,6 +98,50 @@ def elementwise_worst(a, b, scale):
     return float((np.abs(a - b) / np.maximum(scale, 1e-30)).max()) if a.size else 0.0
 
 
+# ---- graphs with chosen row lengths and column counts (tests/test_segment_reference.py, tests/test_gpu_hub_rows.py) ---------------
+# every length at which the hub route of agg.hip changes: empty, one entry, either side of kLongRow = 512 (512 is still a short
+# row, 513 has a second segment of ONE entry), either side of two and three full segments, and a six-segment row
+HUB_LENGTHS = (0, 1, 511, 512, 513, 1023, 1024, 1025, 1536, 1537, 2600)
+
+
+def hub_length_layout(n, rng, fill=3):
+    """lengths [n] holding HUB_LENGTHS where position matters: a hub as row 0 beside an empty row, 513 / 1023 / 1024 / 1025 as
+    adjacent rows, a hub between two empty rows in the middle, a hub as the last row; every other row has 1..fill entries, but
+    for some empty ones"""
+    assert n >= 64
+    lens = rng.integers(1, fill + 1, n).astype(np.int64)
+    lens[rng.choice(np.arange(16, n // 2 - 2), 24, replace=False)] = 0
+    lens[:9] = [2600, 0, 1, 511, 512, 513, 1023, 1024, 1025]
+    lens[n // 2 - 1:n // 2 + 2] = [0, 1536, 0]
+    lens[n - 1] = 1537
+    assert set(HUB_LENGTHS) <= set(lens.tolist())
+    return lens
+
+
+def spread_lengths(total, where):
+    """lengths over the positions where `where` holds that add up to total, as even as they can be"""
+    where = np.asarray(where, bool)
+    m = int(where.sum())
+    out = np.zeros(where.size, np.int64)
+    out[where] = total // m
+    out[np.nonzero(where)[0][:total % m]] += 1
+    return out
+
+
+def graph_from_lengths(row_len, col_len, rng, edge_cols=0):
+    """(adj_ia, adj_ja) of a multigraph whose row r has row_len[r] entries and whose column u is listed col_len[u] times (the two
+    add up to the same): the columns are a random permutation of the multiset.  edge_cols > 0: every entry carries a random edge
+    column 1..edge_cols, about one in eight none (0)"""
+    row_len, col_len = np.asarray(row_len, np.int64), np.asarray(col_len, np.int64)
+    assert row_len.sum() == col_len.sum()
+    ia = np.concatenate([[1], 1 + np.cumsum(row_len)]).astype(np.int32)
+    ja = np.zeros((2, int(row_len.sum())), np.int32, order="F")
+    ja[0] = rng.permutation(np.repeat(np.arange(1, col_len.size + 1), col_len))
+    if edge_cols:
+        ja[1] = np.where(rng.integers(0, 8, ja.shape[1]) == 0, 0, rng.integers(1, edge_cols + 1, ja.shape[1]))
+    return ia, ja
+
+
 # ---- operands at chosen alignments, between guards (tests/test_gpu_unaligned.py) ---------------------------------------------------
 # A torch allocation starts on a 256-byte boundary and is rounded up to 512 bytes, so a fresh tensor never shows what a kernel does
 # with a pointer that is only 4- or 8-byte aligned, nor a store a few elements past the end.  placed / placed_out put an operand k

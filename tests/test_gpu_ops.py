@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import segment_reference as sr
 from helpers import assert_close, assert_close_elementwise, csr_from_index_list, golden, random_graph, rel_err
 
 pytestmark = pytest.mark.gpu
@@ -134,6 +135,11 @@ def test_kipf_ragged_degrees_and_hubs(dev, oracle):
     assert np.array_equal(d[cdeg <= 512], do[cdeg <= 512])
     assert_close(d, do, 1e-5, "hub columns")
     assert_close_elementwise(d, do, oracle.kipf_propagate_bwd(np.abs(x), ia, ja), 1e-5, "hub columns, element-wise")
+    # the segmented sum is a fixed fp32 expression (tests/segment_reference.py): the whole tensors, hubs included, bit for bit
+    assert np.array_equal(y, sr.kipf_propagate(x, ia, ja)), "fwd differs from the segmented-sum yardstick"
+    assert np.array_equal(d, sr.kipf_propagate_bwd(x, ia, ja)), "plain reverse differs from the segmented-sum yardstick"
+    de = H(ops.kipf_propagate_bwd(g, T(x, dev), exact=True))
+    assert np.array_equal(de, sr.kipf_propagate_bwd(x, ia, ja, exact=True)), "exact reverse differs from the segmented-sum yardstick"
 
 
 def test_kipf_empty_and_single(dev, oracle):
@@ -952,6 +958,12 @@ def test_kipf_fuzz_shapes_and_degree_distributions(dev, oracle, seed):
     assert np.array_equal(d[cdeg <= 512], do[cdeg <= 512])
     if nnz:
         assert_close(d, do, 1e-5, "bwd")
+    # ... and the whole tensors against the segmented-sum yardstick (tests/segment_reference.py), hubs included, bit for bit
+    assert np.array_equal(y, sr.kipf_propagate(x, ia, ja, row_deg, col_deg)), "fwd differs from the yardstick"
+    assert np.array_equal(d, sr.kipf_propagate_bwd(gr, ia, ja, n_out=n_cols, row_deg=row_deg, col_deg=col_deg)), "plain reverse differs from the yardstick"
+    de = H(ops.kipf_propagate_bwd(g, T(gr, dev), exact=True))
+    assert np.array_equal(de, sr.kipf_propagate_bwd(gr, ia, ja, exact=True, n_out=n_cols, row_deg=row_deg, col_deg=col_deg)), \
+        "exact reverse differs from the yardstick"
 
 
 @pytest.mark.parametrize("d,loops,N,hubs,directed", [(3, False, 2101, (150, 37), False), (2, True, 2101, (40,), False), (1, False, 203, (), False),
