@@ -45,6 +45,7 @@ _PROTOS = {
     "athena_mp_periodic_pairs": [_i32, _i32, _vp, _vp, _vp, _vp, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp],
     "athena_mp_periodic_graph_host": [_i32, _i32, _vp, _vp, _vp, _vp, _f32, _f32, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp,
                                       _vp],
+    "athena_mp_periodic_stats": [C.POINTER(_i64)],
     "athena_mp_edge_grad_to_points": [_vp, _i32, _vp, _vp],
     "athena_mp_periodic_grad": [_vp, _i32, _i32, _vp, _vp, _vp, _f32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp],
     "athena_mp_edge_grad_to_points_host": [_vp, _i32, _vp, _vp],

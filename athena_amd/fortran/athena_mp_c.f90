@@ -51,7 +51,7 @@ module athena_mp_c
   public :: athena_mp_kipf_layer_fwd, athena_mp_kipf_layer_bwd_x, athena_mp_activation_bwd
   public :: athena_mp_csr_from_edges, athena_mp_graph_export, athena_mp_graph_create_from_edges
   public :: athena_mp_graph_create_from_edges_dev, athena_mp_radius_pairs, athena_mp_radius_graph_host
-  public :: athena_mp_periodic_pairs, athena_mp_periodic_graph_host
+  public :: athena_mp_periodic_pairs, athena_mp_periodic_graph_host, athena_mp_periodic_stats
   public :: athena_mp_edge_grad_to_points, athena_mp_periodic_grad
   public :: athena_mp_edge_grad_to_points_host, athena_mp_periodic_grad_host
   public :: athena_mp_batch_plan_create, athena_mp_batch_plan_destroy, athena_mp_batch_select
@@ -541,6 +541,12 @@ module athena_mp_c
        type(c_ptr), value :: adj_ia, adj_ja, feature, vec, first_count, edge_offsets
        integer(c_int64_t), value :: capacity, edge_capacity
        integer(c_int64_t), intent(out) :: nnz, n_pairs
+     end function
+     !! what the most recent periodic build did: structures walked, structures through the cell grid, pairs of the walk,
+     !! candidate pairs of the grid, structures that qualified for the grid but took the walk
+     integer(c_int) function athena_mp_periodic_stats(stats) bind(C, name="athena_mp_periodic_stats")
+       import :: c_int, c_int64_t
+       integer(c_int64_t), intent(out) :: stats(5)
      end function
      !! geometry gradients, the reverse step of the two builders (definition: include/athena_mp.h).  The reverse of
      !! athena_mp_radius_pairs: dcoords (dim, E) on the device -> dpoints (dim, n) on the device, a signed sum over the handle's rows

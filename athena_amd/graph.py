@@ -34,6 +34,18 @@ def _structure_arrays(frac, lat, offsets, pbc):
     return frac, lat, off, pbc3
 
 
+PERIODIC_STATS = ("structures_walked", "structures_grid", "walk_pairs", "grid_pairs", "grid_fallbacks")
+
+
+def periodic_stats():
+    """What the most recent periodic build of the process did (athena_mp_periodic_stats), as a dict: structures that took the
+    walk over every pair / the cell grid, atom pairs i <= j each route examined, and structures that qualified for the grid but
+    took the walk (a fractional coordinate beyond +-64, lattice vectors too long for the cutoff, or no periodic axis)."""
+    out = (C.c_int64 * 5)()
+    _capi.call("athena_mp_periodic_stats", out)
+    return dict(zip(PERIODIC_STATS, (int(v) for v in out)))
+
+
 class graph_type:
     """Undirected sparse graph in athena's CSR convention."""
 

@@ -174,6 +174,14 @@ int athena_mp_periodic_graph_host(int32_t n_structures, int32_t n_atoms, const i
                                   int32_t add_self_loops, int32_t *adj_ia_out, int32_t *adj_ja_out, int64_t capacity,
                                   int64_t *nnz_out, float *feature_out, float *vec_out, int32_t *first_count_out,
                                   int64_t edge_capacity, int64_t *n_pairs_out, int64_t *edge_offsets_out);
+/* What the most recent athena_mp_periodic_pairs pass of the process did (athena_mp_periodic_graph_host runs two: the last one
+ * counts).  The builder has two routes with the same outputs, byte for byte, chosen per structure: the walk over every pair
+ * i <= j, and a cell grid in fractional coordinates that prunes the pairs of large cells first (periodic_graph.hip proves the rule;
+ * ATHENA_MP_PERIODIC_ROUTE = auto | walk | grid pins the route in tests).  Empty structures count nowhere.
+ *   out[0] structures walked;  out[1] structures through the grid;  out[2] pairs i <= j examined by the walk;
+ *   out[3] candidate pairs examined by the grid;  out[4] structures that qualified for the grid but took the walk because a
+ *   fractional coordinate is beyond +-64, the lattice vectors are too long for the cutoff, or no axis is periodic. */
+int athena_mp_periodic_stats(int64_t out[5]);
 /* Geometry gradients (geometry_grad.hip): the reverse step of the two builders above.  The layers return their gradient per edge,
  * in HBM (athena_mp_gno_aggregate_bwd_coords: dcoords [E, d]; athena_mp_duvenaud_propagate_bwd_e: de [E, F_e]); these entries carry
  * it back to the points, the atoms and the cell.  Nothing in the reference corresponds to them (its edge geometry carries no

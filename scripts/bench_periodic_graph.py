@@ -11,7 +11,14 @@ atoms, half in cubic and half in skewed cells, cutoffs 0.5 / 3.0 as in get_graph
 After one warm-up build of each, the median of --repeats (device) / --host-repeats (host) builds, host clock around a call that ends
 in a device synchronise.  The two routes use one definition: the arrays are compared for equality.
 
+The large-cell leg (--large-cells: that leg alone, appended to --out) times athena_mp_periodic_pairs (size query + fill of every
+output) on single cubic structures of 128 ... 32 768 atoms at the density of 4096 atoms in a cell of edge 38.4 (the edge grows
+with the cube root of the atom count) and on a batch of 64 structures of 1000 atoms, with ATHENA_MP_PERIODIC_ROUTE = walk and
+= grid pinned in turn, alternating in one process; the arrays of the two routes are compared, and athena_mp_periodic_stats of
+each build is printed.  It is what kGridAtoms of periodic_graph.hip, the automatic threshold between the routes, rests on.
+
   python scripts/bench_periodic_graph.py [--structures 130000] [--repeats 5] [--host-repeats 1] [--out profiles/periodic_graph_build.txt]
+  python scripts/bench_periodic_graph.py --large-cells [--repeats 5]         (appends to --out)
   rocprofv3 --kernel-trace --stats -d DIR -- python scripts/bench_periodic_graph.py --device-only --repeats 2 --out -
 """
 import argparse
@@ -42,8 +49,86 @@ def make_batch(B, seed=2):
     return frac, lat.astype(np.float32), off
 
 
+LARGE_SIZES = (128, 256, 512, 1024, 4096, 32768)
+
+
+def large_cells(a):
+    """single large cells and a batch of 64 x 1000 atoms, walk against grid; returns the lines of the report"""
+    import ctypes as C
+
+    import torch
+
+    from athena_amd import _capi
+    from athena_amd.graph import periodic_stats
+
+    dev = torch.device("cuda:0")
+    cmin, cmax = 0.5, 3.0
+    density = 4096 / 38.4 ** 3
+    rng = np.random.Generator(np.random.PCG64(9))
+    cases = []
+    for m in LARGE_SIZES:
+        edge = (m / density) ** (1.0 / 3.0)
+        cases.append((f"1 x {m} atoms, edge {edge:.2f}", rng.random((m, 3)).astype(np.float32),
+                      (np.eye(3) * edge).astype(np.float32)[None], np.array([0, m], np.int32)))
+    edge = (1000 / density) ** (1.0 / 3.0)
+    cases.append((f"64 x 1000 atoms, edge {edge:.2f}", rng.random((64000, 3)).astype(np.float32),
+                  np.tile((np.eye(3) * edge).astype(np.float32), (64, 1, 1)), (np.arange(65) * 1000).astype(np.int32)))
+    pbc = np.ones(3, np.int32)
+    vp = lambda x: x.ctypes.data_as(C.c_void_p)
+    ptr = lambda t: C.c_void_p(t.data_ptr())
+
+    def build(route, fd, ld, off):
+        """size query, allocation of the outputs, fill: seconds, the output tensors, the stats"""
+        os.environ["ATHENA_MP_PERIODIC_ROUTE"] = route
+        B, n = ld.shape[0], fd.shape[0]
+        head = (B, n, vp(off), ptr(fd), ptr(ld), vp(pbc), cmin, cmax)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        E = C.c_int64()
+        _capi.call("athena_mp_periodic_pairs", *head, None, None, None, None, None, 0, C.byref(E), None)
+        pairs = torch.empty((E.value, 2), dtype=torch.int32, device=dev)
+        feature = torch.empty((E.value,), dtype=torch.float32, device=dev)
+        vec = torch.empty((E.value, 3), dtype=torch.float32, device=dev)
+        shift = torch.empty((E.value, 3), dtype=torch.int32, device=dev)
+        first = torch.empty((n,), dtype=torch.int32, device=dev)
+        eoff = np.zeros(B + 1, np.int64)
+        _capi.call("athena_mp_periodic_pairs", *head, ptr(pairs), ptr(feature), ptr(vec), ptr(shift), ptr(first), E.value, C.byref(E),
+                   vp(eoff))
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, (pairs, feature, vec, shift, first), periodic_stats()
+
+    lines = [f"# large cells, scripts/bench_periodic_graph.py --large-cells on {torch.cuda.get_device_name(0)}: athena_mp_periodic_pairs, size "
+             f"query + fill of every output, cutoffs {cmin:g} / {cmax:g}, random atoms at {density:.4f} per cubic unit",
+             f"# the route pinned with ATHENA_MP_PERIODIC_ROUTE, walk and grid alternating in one process; one warm-up build of each, then "
+             f"median (min - max) of {a.repeats}; host clock around calls that end in a device synchronise; seconds"]
+    old = os.environ.get("ATHENA_MP_PERIODIC_ROUTE")
+    try:
+        for name, frac, lat, off in cases:
+            fd, ld = torch.from_numpy(frac).to(dev), torch.from_numpy(lat).to(dev)
+            _, walk, sw = build("walk", fd, ld, off)
+            _, grid, sg = build("grid", fd, ld, off)
+            assert all(torch.equal(x.view(torch.int32), y.view(torch.int32)) for x, y in zip(walk, grid)), f"{name}: the routes differ"
+            E = int(walk[1].shape[0])
+            del walk, grid
+            tw, tg = [], []
+            for _ in range(a.repeats):
+                tw.append(build("walk", fd, ld, off)[0])
+                tg.append(build("grid", fd, ld, off)[0])
+            mw, mg = statistics.median(tw), statistics.median(tg)
+            lines.append(f"{name:32s} edges {E:9d}  walk {mw:.5f} ({min(tw):.5f} - {max(tw):.5f})  grid {mg:.5f} ({min(tg):.5f} - {max(tg):.5f})  "
+                         f"walk / grid {mw / mg:7.2f}  walk pairs {sw['walk_pairs']}  grid pairs {sg['grid_pairs']}  "
+                         f"grid structures {sg['structures_grid']}  identical arrays")
+    finally:
+        if old is None:
+            os.environ.pop("ATHENA_MP_PERIODIC_ROUTE", None)
+        else:
+            os.environ["ATHENA_MP_PERIODIC_ROUTE"] = old
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--large-cells", action="store_true", help="only the large-cell leg (walk against grid), appended to --out")
     ap.add_argument("--structures", type=int, default=130_000)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--host-repeats", type=int, default=1)
@@ -58,6 +143,13 @@ def main():
 
     assert torch.cuda.is_available(), "needs the MI355X: a CPU run says nothing about these times"
     _capi.init(0)
+    if a.large_cells:
+        text = "\n".join(large_cells(a))
+        print(text)
+        if a.out != "-":
+            with open(a.out, "a") as f:
+                f.write(text + "\n")
+        return
     dev = torch.device("cuda:0")
     B = a.structures
     cmin, cmax = 0.5, 3.0
