@@ -5,10 +5,10 @@ kipf / duvenaud / graph_nop message-passing layers as hand-written gfx950 HIP ke
 C ABI (include/athena_mp.h), plus the host-side mirrors of the reference interface.
 """
 from . import _capi  # noqa: F401
-from .graph import DeviceGraph, graph_type  # noqa: F401
+from .graph import DeviceGraph, duvenaud_plan_stats, graph_type  # noqa: F401
 from . import geometry  # noqa: F401
 from .geometry import points_grad, structures_grad, structures_grad_host  # noqa: F401
 from . import batching  # noqa: F401
 from .batching import Batch, DeviceDataset  # noqa: F401
 
-__all__ = ["_capi", "DeviceGraph", "graph_type", "geometry", "points_grad", "structures_grad", "structures_grad_host", "batching", "Batch", "DeviceDataset"]
+__all__ = ["_capi", "DeviceGraph", "duvenaud_plan_stats", "graph_type", "geometry", "points_grad", "structures_grad", "structures_grad_host", "batching", "Batch", "DeviceDataset"]

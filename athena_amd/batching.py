@@ -102,9 +102,11 @@ class DeviceDataset:
                    eoff.ctypes.data_as(C.c_void_p), None, None)
         return voff, eoff
 
-    def select(self, ids, vertex_map=None, edge_map=None):
+    def select(self, ids, vertex_map=None, edge_map=None, plan_degrees=None):
         """The batch of the structures `ids` (0-based, any order, repeats allowed) as a Batch.  vertex_map / edge_map: contiguous int32
-        device tensors of the batch's vertex / edge-column count to write the maps into."""
+        device tensors of the batch's vertex / edge-column count to write the maps into.  plan_degrees = (min_deg, max_deg): the
+        child's Duvenaud degree-bucket plan is built behind the select, on the same stream (DeviceGraph.plan_duvenaud), so the first
+        layer call on the batch does not stop to build it."""
         import torch
 
         if self._plan is None:
@@ -127,6 +129,8 @@ class DeviceDataset:
         rows = (int(self.vertex_offsets[-1]), int(self.edge_offsets[-1]) if self.edge_offsets is not None else 0, self.num_structures)
         b = Batch(DeviceGraph.borrow(child), voff, eoff, maps[0], maps[1], sel.copy(), rows)
         b.handle._borrowed = False                                             # the batch owns its child: close() destroys it
+        if plan_degrees is not None:
+            b.handle.plan_duvenaud(*plan_degrees)
         return b
 
     def batches(self, batch_size, shuffle=True, seed=0, drop_last=False):

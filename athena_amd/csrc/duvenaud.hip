@@ -138,82 +138,6 @@ __global__ void softmax_segsum_bwd_kernel(int O, int64_t N, int S, const int32_t
 } // namespace
 
 namespace amp {
-// stable sort of the vertices by degree bucket (host, once per (min,max)); each bucket becomes one
-// contiguous run of g->bucket_perm so the bucketed update is <= D dense contractions with row indirection
-int duvenaud_buckets(const athena_mp_graph *g, int min_deg, int max_deg)
-{
-    if (g->bucket_perm && g->bucket_min == min_deg && g->bucket_max == max_deg) return 0;
-    const int nb = max_deg - min_deg + 1;
-    const int32_t n = g->n_rows;
-    std::vector<int64_t> off(nb + 1, 0);
-    std::vector<int32_t> bucket(n);
-    for (int32_t v = 0; v < n; ++v) {
-        int d = std::max(min_deg, std::min(g->h_deg_row[v], max_deg)) - min_deg; // 0-based
-        bucket[v] = d;
-        off[d + 1]++;
-    }
-    for (int b = 0; b < nb; ++b) off[b + 1] += off[b];
-    std::vector<int32_t> perm(n);
-    {
-        std::vector<int64_t> pos(off.begin(), off.end() - 1);
-        for (int32_t v = 0; v < n; ++v) perm[pos[bucket[v]]++] = v;
-    }
-    std::vector<int32_t> tstart, tinfo, toff(nb + 1, 0);
-    for (int b = 0; b < nb; ++b) {
-        for (int64_t i = off[b]; i < off[b + 1]; i += 16) {
-            tstart.push_back((int32_t)i);
-            tinfo.push_back((b << 8) | (int32_t)std::min<int64_t>(16, off[b + 1] - i));
-        }
-        toff[b + 1] = (int32_t)tstart.size();
-    }
-    if (g->bucket_perm) {
-        AMP_HIP(hipStreamSynchronize(stream()));
-        AMP_HIP(hipFree(g->bucket_perm));
-        AMP_HIP(hipFree(g->btile_start));
-        AMP_HIP(hipFree(g->btile_info));
-        AMP_HIP(hipFree(g->btile_rows));
-        AMP_HIP(hipFree(g->btile_off_dev));
-        g->bucket_perm = g->btile_start = g->btile_info = g->btile_rows = g->btile_off_dev = nullptr;
-    }
-    const size_t nt = tstart.size();
-    // four copies back to back, [16 nt] each:
-    //   0  padding slots as ~(first vertex of the tile): the weight-gradient kernel zeroes their gradient rows
-    //   1  padding slots as the first vertex itself: the row kernels load and store them as benign duplicates
-    //   2  copy 1 transposed 4 x 4 inside each tile (slot 4 i + r at position 4 r + i): a lane that serves rows r, 4 + r,
-    //      8 + r, 12 + r of a tile in four coalesced loads fetches its four ids with one 16-byte load
-    //   3  copy 0 transposed the same way
-    std::vector<int32_t> trows(64 * nt);
-    for (size_t t = 0; t < nt; ++t) {
-        const int cnt = tinfo[t] & 255;
-        for (int i = 0; i < 16; ++i) {
-            const int32_t v = i < cnt ? perm[tstart[t] + i] : perm[tstart[t]];
-            const int32_t sv = i < cnt ? v : ~v;
-            const int tp = 4 * (i & 3) + (i >> 2);
-            trows[16 * t + i] = sv;
-            trows[16 * (nt + t) + i] = v;
-            trows[16 * (2 * nt + t) + tp] = v;
-            trows[16 * (3 * nt + t) + tp] = sv;
-        }
-    }
-    AMP_HIP(hipMalloc((void **)&g->btile_rows, sizeof(int32_t) * (nt ? 64 * nt : 1)));
-    if (nt) AMP_HIP(hipMemcpy(g->btile_rows, trows.data(), sizeof(int32_t) * 64 * nt, hipMemcpyHostToDevice));
-    AMP_HIP(hipMalloc((void **)&g->bucket_perm, sizeof(int32_t) * (n ? n : 1)));
-    AMP_HIP(hipMalloc((void **)&g->btile_start, sizeof(int32_t) * (nt ? nt : 1)));
-    AMP_HIP(hipMalloc((void **)&g->btile_info, sizeof(int32_t) * (nt ? nt : 1)));
-    AMP_HIP(hipMalloc((void **)&g->btile_off_dev, sizeof(int32_t) * (nb + 1)));
-    if (n) AMP_HIP(hipMemcpy(g->bucket_perm, perm.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice));
-    if (nt) {
-        AMP_HIP(hipMemcpy(g->btile_start, tstart.data(), sizeof(int32_t) * nt, hipMemcpyHostToDevice));
-        AMP_HIP(hipMemcpy(g->btile_info, tinfo.data(), sizeof(int32_t) * nt, hipMemcpyHostToDevice));
-    }
-    AMP_HIP(hipMemcpy(g->btile_off_dev, toff.data(), sizeof(int32_t) * (nb + 1), hipMemcpyHostToDevice));
-    g->n_btiles = (int32_t)nt;
-    g->btile_off = toff;
-    g->bucket_off = off;
-    g->bucket_min = min_deg;
-    g->bucket_max = max_deg;
-    return 0;
-}
 // a = [a_x | a_e] packed into the library's workspace (slot 16): the way shapes outside the split kernels take a split a
 int duv_pack_a(const athena_mp_graph *g, int32_t Fv, int32_t Fe, const float *a_x, const float *a_e, const float **packed)
 {

@@ -55,6 +55,7 @@ module athena_mp_c
   public :: athena_mp_edge_grad_to_points, athena_mp_periodic_grad
   public :: athena_mp_edge_grad_to_points_host, athena_mp_periodic_grad_host
   public :: athena_mp_batch_plan_create, athena_mp_batch_plan_destroy, athena_mp_batch_select
+  public :: athena_mp_duvenaud_plan, athena_mp_duvenaud_plan_export, athena_mp_duvenaud_plan_stats
   public :: athena_mp_error_message
   public :: athena_mp_pull_gemm, athena_mp_dev_offset, athena_mp_kipf_layer_bwd
   public :: athena_mp_comm_create, athena_mp_comm_create_from_file, athena_mp_comm_destroy, athena_mp_comm_barrier
@@ -613,6 +614,28 @@ module athena_mp_c
        type(c_ptr), value :: plan, child, offsets_out, edge_offsets_out, vertex_map_dev, edge_map_dev
        integer(c_int32_t), value :: n_sel
        integer(c_int32_t), intent(in) :: sel(*)
+     end function
+     !! the Duvenaud degree-bucket plan of a handle (definition: include/athena_mp.h): built now, on the library's stream; a no-op
+     !! when the handle already holds the plan of (min_deg, max_deg).  Called right after athena_mp_batch_select on the child
+     integer(c_int) function athena_mp_duvenaud_plan(graph, min_deg, max_deg) bind(C, name="athena_mp_duvenaud_plan")
+       import :: c_int, c_int32_t, c_ptr
+       type(c_ptr), value :: graph
+       integer(c_int32_t), value :: min_deg, max_deg
+     end function
+     !! one array of the plan back on the host (which 0..6: see include/athena_mp.h; 5 is int64); host_dst = c_null_ptr queries count
+     integer(c_int) function athena_mp_duvenaud_plan_export(graph, which, host_dst, capacity, count) &
+          bind(C, name="athena_mp_duvenaud_plan_export")
+       import :: c_int, c_int32_t, c_int64_t, c_ptr
+       type(c_ptr), value :: graph, host_dst
+       integer(c_int32_t), value :: which
+       integer(c_int64_t), value :: capacity
+       integer(c_int64_t), intent(out) :: count
+     end function
+     !! plans built on the host / on the device by this process, requests served by a plan the handle already held
+     integer(c_int) function athena_mp_duvenaud_plan_stats(host_builds, device_builds, reused) &
+          bind(C, name="athena_mp_duvenaud_plan_stats")
+       import :: c_int, c_int64_t
+       integer(c_int64_t), intent(out) :: host_builds, device_builds, reused
      end function
      !! one array of the handle back on the host (which: see include/athena_mp.h); host_dst = c_null_ptr queries count
      integer(c_int) function athena_mp_graph_export(graph, which, host_dst, capacity, count) &

@@ -46,6 +46,14 @@ def periodic_stats():
     return dict(zip(PERIODIC_STATS, (int(v) for v in out)))
 
 
+def duvenaud_plan_stats():
+    """Degree-bucket plans this process built on the host / on the device, and requests served by a plan the handle already held
+    (athena_mp_duvenaud_plan_stats), as a dict."""
+    h, d, r = C.c_int64(), C.c_int64(), C.c_int64()
+    _capi.call("athena_mp_duvenaud_plan_stats", C.byref(h), C.byref(d), C.byref(r))
+    return {"host_builds": int(h.value), "device_builds": int(d.value), "reused": int(r.value)}
+
+
 class graph_type:
     """Undirected sparse graph in athena's CSR convention."""
 
@@ -335,6 +343,32 @@ class DeviceGraph:
         _capi.call("athena_mp_graph_export", self.handle, which, None, 0, C.byref(n))
         out = np.empty(n.value, dt)
         _capi.call("athena_mp_graph_export", self.handle, which, out.ctypes.data_as(C.c_void_p), n.value, C.byref(n))
+        return out
+
+    _PLAN_ARRAYS = {"bucket_perm": (0, np.int32), "btile_start": (1, np.int32), "btile_info": (2, np.int32),
+                    "btile_rows": (3, np.int32), "btile_off_dev": (4, np.int32), "bucket_off": (5, np.int64),
+                    "btile_off": (6, np.int32)}
+
+    def plan_duvenaud(self, min_deg, max_deg):
+        """Build the Duvenaud degree-bucket plan of (min_deg, max_deg) now, on torch's current stream (athena_mp_duvenaud_plan; the
+        definition is in include/athena_mp.h): the first layer call on this handle then finds it.  A no-op when the handle already
+        holds that plan.  Returns self."""
+        _capi.use_torch_stream()
+        _capi.call("athena_mp_duvenaud_plan", self.handle, int(min_deg), int(max_deg))
+        return self
+
+    def export_duvenaud_plan(self):
+        """the seven arrays of the handle's degree-bucket plan as numpy (athena_mp_duvenaud_plan_export): bucket_perm, btile_start,
+        btile_info, btile_rows [4, 16 nt], btile_off_dev, and the host tables bucket_off (int64) and btile_off"""
+        _capi.use_torch_stream()
+        out = {}
+        for name, (which, dt) in self._PLAN_ARRAYS.items():
+            n = C.c_int64()
+            _capi.call("athena_mp_duvenaud_plan_export", self.handle, which, None, 0, C.byref(n))
+            a = np.empty(n.value, dt)
+            _capi.call("athena_mp_duvenaud_plan_export", self.handle, which, a.ctypes.data_as(C.c_void_p), n.value, C.byref(n))
+            out[name] = a
+        out["btile_rows"] = out["btile_rows"].reshape(4, -1)
         return out
 
     @classmethod

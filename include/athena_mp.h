@@ -300,6 +300,36 @@ int athena_mp_batch_plan_destroy(athena_mp_batch_plan *p);
 int athena_mp_batch_select(const athena_mp_batch_plan *p, int32_t n_sel, const int32_t *sel_host, athena_mp_graph **out,
                            int32_t *offsets_out, int64_t *edge_offsets_out, int32_t *vertex_map_dev, int32_t *edge_map_dev);
 
+/* The Duvenaud degree-bucket plan of a handle (bucket_plan.hip): what the bucketed update kernels (duv_mfma.hip) read.  A layer call
+ * builds it on first use for its (min_deg, max_deg); athena_mp_duvenaud_plan builds it NOW, on the library's stream -- a training loop
+ * calls it right after athena_mp_batch_select, so the first layer call on the fresh child finds it.  A no-op when the handle already
+ * holds the plan of that (min_deg, max_deg); another pair replaces the plan (that waits for the stream, then frees the old arrays).
+ * Definition, with deg[0..n) the handle's row degrees (athena_mp_graph_export 11), min_deg <= max_deg, nb = max_deg - min_deg + 1:
+ *     bucket[v] = clamp(deg[v], min_deg, max_deg) - min_deg
+ *     bucket_perm [n]     the vertices sorted by bucket, STABLE: equal buckets keep vertex order
+ *     bucket_off [nb + 1] (int64, host) the bucket starts in bucket_perm
+ *     tiles: every bucket cut into runs of 16, bucket-major, nt of them;  btile_start[t] = first index into bucket_perm,
+ *     btile_info[t] = bucket << 8 | count (count 1..16),  btile_off [nb + 1] = first tile of each bucket (on the host and in HBM)
+ *     btile_rows [4][16 nt]: slot i of tile t has v = bucket_perm[start + (i < count ? i : 0)], sv = i < count ? v : ~v;
+ *       copy 0 holds sv at 16 t + i, copy 1 holds v there, copies 2 and 3 are copies 1 and 0 transposed 4 x 4 inside the tile
+ *       (slot i at position 4 (i & 3) + (i >> 2))
+ * Two routes write these arrays byte for byte alike.  host: one pass over the handle's host copy of the degrees, a counting sort,
+ * five blocking uploads.  device: the host only counts (the sizes and the two host tables); the keys, one stable 8-bit counting pass
+ * (hence nb <= 256), the tile offsets and the tile slots are made in HBM with no copy in either direction and no synchronise on a
+ * handle's first plan (the library's scratch for the sort grows with the largest handle planned so far; growing it waits for the
+ * stream).  ATHENA_MP_BUCKET_PLAN = auto | host | device pins the route (tests only, read at every build).  auto: device when
+ * n_rows > 0 and nb <= 256, host otherwise; device with nb > 256 is refused with a message that names the limit.  A failed build
+ * leaves no plan behind.
+ * athena_mp_duvenaud_plan_export: one array of the plan on the host, with athena_mp_graph_export's convention (host_dst == NULL
+ * queries count; capacity and count in elements).  which: 0 bucket_perm, 1 btile_start, 2 btile_info, 3 btile_rows (64 nt),
+ * 4 btile_off in HBM, 5 bucket_off (int64, the host table), 6 btile_off (the host table); int32 except 5.  Refused when the handle
+ * has no plan.
+ * athena_mp_duvenaud_plan_stats: plans this process built on the host / on the device, and requests served by the plan a handle
+ * already held (each may be NULL). */
+int athena_mp_duvenaud_plan(const athena_mp_graph *g, int32_t min_deg, int32_t max_deg);
+int athena_mp_duvenaud_plan_export(const athena_mp_graph *g, int32_t which, void *host_dst, int64_t capacity, int64_t *count);
+int athena_mp_duvenaud_plan_stats(int64_t *host_builds, int64_t *device_builds, int64_t *reused);
+
 /* ---- Kipf --------------------------------------------------------------- */
 /* kipf_propagate, athena_diffstruc_extd_sub_kipf.f90:7-59
  *   y[v,:] = sum_w ((deg_v*deg_u)^-1/2) x[u,:]        x [n_cols,F], y [n_rows,F] */
