@@ -42,6 +42,8 @@ _PROTOS = {
     "athena_mp_graph_create_from_edges_dev": [_i32, _i64, _vp, _i32, _i32, _vp, _vp, _i64, _vp, C.POINTER(_vp)],
     "athena_mp_radius_pairs": [_i32, _i32, _vp, _f32, _vp, _vp, _i64, _vp],
     "athena_mp_radius_graph_host": [_i32, _i32, _vp, _f32, _i32, _vp, _vp, _i64, _vp, _vp, _i64, _vp],
+    "athena_mp_radius_pairs_batched": [_i32, _i32, _vp, _i32, _vp, _f32, _vp, _vp, _i64, _vp, _vp],
+    "athena_mp_radius_graph_batched_host": [_i32, _i32, _vp, _i32, _vp, _f32, _i32, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp],
     "athena_mp_periodic_pairs": [_i32, _i32, _vp, _vp, _vp, _vp, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp],
     "athena_mp_periodic_graph_host": [_i32, _i32, _vp, _vp, _vp, _vp, _f32, _f32, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp,
                                       _vp],

@@ -413,3 +413,415 @@ extern "C" int athena_mp_radius_graph_host(int32_t n, int32_t dim, const float *
     *nnz_out = nnz_built;
     return 0;
 }
+
+// ---- a batch of clouds: one block-diagonal pair list, a grid per cloud --------------------------------------------------------------
+// The definition (include/athena_mp.h): the pair lists radius_pairs_core gives for the slices points[offsets[b] : offsets[b+1]],
+// in cloud order, offsets[b] added to both indices; edge_offsets[b] = pairs whose i is below offsets[b].
+//
+// How: the host cuts the clouds into work items (cloud, points p0 .. p1-1) of at most kItemPoints points, one 64-lane wave each.
+// A bounding box per item (min and max are order-free; a wave folds with __shfl_xor and writes its own slot), folded per cloud in
+// item order; the boxes come home and make_grid runs per cloud, unchanged -- so the margin proof above holds for every cloud with
+// its own n: cells at least radius * (1 + 2^-10) wide, at most kMaxCellsAxis per axis, at most 2 m_b per cloud, at most 2 n in
+// all.  A cloud's cells are the keys [cell_base[b], cell_base[b+1]): disjoint ranges, so after the key pass no kernel sees a
+// candidate pair of two clouds.  From there on the passes are those of the single cloud over all points at once -- sort of (cell,
+// id), positions in cell order, cell starts, COUNT, 64-bit scan in point-id order, FILL, one sort, emit -- with a thread looking
+// up its cloud (the last b with offsets[b] <= i: empty clouds repeat a value and own no point) and loading that cloud's grid.
+// Both ends of a pair are in one cloud, so the key is i * M + (j - offsets[b]) with M the largest cloud: the order is that of
+// (i, j), in fewer bits than i * n + j.  No atomics on data; every access to points and coords is 4 bytes wide.
+namespace {
+
+constexpr int kItemPoints = 4096;
+constexpr int kItemWaves = 4;        // work items per 256-thread block
+
+__device__ inline Box box_wave_reduce(Box b)
+{
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+        Box o;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            o.lo[k] = __shfl_xor(b.lo[k], d, 64);
+            o.hi[k] = __shfl_xor(b.hi[k], d, 64);
+        }
+        o.first_bad = __shfl_xor(b.first_bad, d, 64);
+        box_fold(b, o);
+    }
+    return b;
+}
+
+// one wave per work item (cloud, p0, p1): the box and the first non-finite point of points p0 .. p1-1 -> partial[item]
+__global__ __launch_bounds__(64 * kItemWaves) void rgb_box_item_kernel(int32_t n_items, const int32_t *__restrict__ items, int dim,
+                                                                       const float *__restrict__ pts, Box *__restrict__ partial)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t w = (int64_t)blockIdx.x * kItemWaves + (threadIdx.x >> 6);
+    if (w >= n_items) return;
+    const int32_t p0 = items[3 * w + 1], p1 = items[3 * w + 2];
+    Box b = box_empty();
+    for (int64_t i = (int64_t)p0 + lane; i < p1; i += 64) {
+        bool ok = true;
+        for (int k = 0; k < dim; ++k) {
+            const float v = pts[i * dim + k];
+            ok = ok && isfinite(v);
+            b.lo[k] = fminf(b.lo[k], v);
+            b.hi[k] = fmaxf(b.hi[k], v);
+        }
+        if (!ok && (unsigned long long)i < b.first_bad) b.first_bad = (unsigned long long)i;
+    }
+    b = box_wave_reduce(b);
+    if (lane == 0) partial[w] = b;
+}
+
+// one thread per cloud: its items' partials in item order (an empty cloud has no item: the empty box).  first_bad stays per
+// cloud; the host, which reads every box anyway, takes the smallest
+__global__ __launch_bounds__(256) void rgb_box_cloud_kernel(int32_t B, const int32_t *__restrict__ item_first,
+                                                            const Box *__restrict__ partial, Box *__restrict__ out)
+{
+    const int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (b >= B) return;
+    Box x = box_empty();
+    for (int32_t w = item_first[b]; w < item_first[b + 1]; ++w) box_fold(x, partial[w]);
+    out[b] = x;
+}
+
+// one wave per work item, so the cloud is known without a search: key = cell_base[cloud] + the cell in the cloud's own grid
+__global__ __launch_bounds__(64 * kItemWaves) void rgb_cell_key_kernel(int32_t n_items, const int32_t *__restrict__ items, int dim,
+                                                                       const float *__restrict__ pts, const Grid *__restrict__ grids,
+                                                                       const uint32_t *__restrict__ cell_base, uint32_t *__restrict__ key)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t w = (int64_t)blockIdx.x * kItemWaves + (threadIdx.x >> 6);
+    if (w >= n_items) return;
+    const int32_t b = items[3 * w], p0 = items[3 * w + 1], p1 = items[3 * w + 2];
+    const Grid g = grids[b];
+    const uint32_t base = cell_base[b];
+    for (int64_t i = (int64_t)p0 + lane; i < p1; i += 64) {
+        uint32_t c = 0;
+        for (int k = dim - 1; k >= 0; --k)
+            c = c * (uint32_t)g.nc[k] + (uint32_t)cell_coord(pts[i * dim + k], g.lo[k], g.inv_w[k], g.nc[k]);
+        key[i] = base + c;
+    }
+}
+
+// the cloud of point i, 0 <= i < offsets[B]: the last b with offsets[b] <= i (empty clouds repeat a value and own no point)
+__device__ inline int32_t cloud_of(int32_t B, const int32_t *__restrict__ offsets, int32_t i)
+{
+    int32_t lo = 0, hi = B;                       // offsets[lo] <= i < offsets[hi]
+    while (hi - lo > 1) {
+        const int32_t mid = lo + ((hi - lo) >> 1);
+        if (offsets[mid] <= i) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// rg_neighbour_kernel with the grid of the slot's cloud and the walk inside that cloud's cells.
+// FILL = true: key[offset[i] + t] = i * M + (j - offsets[cloud]) for the t-th partner found.
+template <int DIM, bool FILL>
+__global__ __launch_bounds__(256) void rgb_neighbour_kernel(int32_t n, int32_t B, const int32_t *__restrict__ offsets,
+                                                            const Grid *__restrict__ grids, const uint32_t *__restrict__ cell_base,
+                                                            unsigned long long M, float r2, const float *__restrict__ sorted,
+                                                            const int32_t *__restrict__ perm, const uint32_t *__restrict__ sorted_key,
+                                                            const int32_t *__restrict__ cell_start, uint32_t *__restrict__ count,
+                                                            const unsigned long long *__restrict__ offset,
+                                                            unsigned long long *__restrict__ key)
+{
+    const int64_t slot = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (slot >= n) return;
+    const int32_t i = perm[slot];
+    const int32_t b = cloud_of(B, offsets, i);
+    const Grid g = grids[b];
+    const uint32_t cb = cell_base[b];
+    const int32_t first_point = offsets[b];
+    float p[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+    for (int a = 0; a < DIM; ++a) p[a] = sorted[slot * DIM + a];
+    uint32_t c = sorted_key[slot] - cb;
+    int32_t cc[3] = {0, 0, 0};
+#pragma unroll
+    for (int a = 0; a < DIM; ++a) {
+        cc[a] = (int32_t)(c % (uint32_t)g.nc[a]);
+        c /= (uint32_t)g.nc[a];
+    }
+    uint32_t found = 0;
+    unsigned long long at = 0;
+    if (FILL) at = offset[i];
+    const int z0 = DIM > 2 ? max(cc[2] - 1, 0) : 0, z1 = DIM > 2 ? min(cc[2] + 1, g.nc[2] - 1) : 0;
+    const int y0 = DIM > 1 ? max(cc[1] - 1, 0) : 0, y1 = DIM > 1 ? min(cc[1] + 1, g.nc[1] - 1) : 0;
+    const int x0 = max(cc[0] - 1, 0), x1 = min(cc[0] + 1, g.nc[0] - 1);
+    for (int z = z0; z <= z1; ++z)
+        for (int y = y0; y <= y1; ++y) {
+            // the cells x0 .. x1 of one grid row are consecutive keys: one contiguous run of slots, all of this cloud
+            const uint32_t row = (DIM > 2 ? (uint32_t)z * (uint32_t)g.nc[1] : 0u) + (uint32_t)y;
+            const uint32_t first = cb + row * (uint32_t)g.nc[0] + (uint32_t)x0;
+            const int32_t beg = cell_start[first], end = cell_start[first + (uint32_t)(x1 - x0) + 1u];
+            for (int32_t m = beg; m < end; ++m) {
+                const int32_t j = perm[m];
+                if (j <= i) continue;
+                if (!joined<DIM>(p, sorted + (int64_t)m * DIM, r2)) continue;       // p_i - p_j, i < j
+                if (FILL) key[at + found] = (unsigned long long)i * M + (unsigned long long)(j - first_point);
+                ++found;
+            }
+        }
+    if (!FILL) count[i] = found;
+}
+
+// edge_offsets[b] = pairs whose i is below offsets[b]: the scan at the cloud starts (b = 0 .. B)
+__global__ __launch_bounds__(256) void rgb_edge_offsets_kernel(int32_t B, int32_t n, const int32_t *__restrict__ offsets,
+                                                               const unsigned long long *__restrict__ offset,
+                                                               const unsigned long long *__restrict__ total,
+                                                               long long *__restrict__ edge_offsets)
+{
+    const int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (b > B) return;
+    const int32_t v = offsets[b];
+    edge_offsets[b] = (long long)(v < n ? offset[v] : *total);
+}
+
+__global__ __launch_bounds__(256) void rgb_emit_kernel(int64_t E, int32_t B, const int32_t *__restrict__ offsets, unsigned long long M,
+                                                       int dim, const unsigned long long *__restrict__ key,
+                                                       const float *__restrict__ pts, int32_t *__restrict__ pairs,
+                                                       float *__restrict__ coords)
+{
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= E) return;
+    const unsigned long long k = key[e];
+    const int64_t i = (int64_t)(k / M);
+    const int64_t j = (int64_t)offsets[cloud_of(B, offsets, (int32_t)i)] + (int64_t)(k % M);
+    if (pairs) {
+        pairs[2 * e] = (int32_t)i + 1;
+        pairs[2 * e + 1] = (int32_t)j + 1;
+    }
+    if (coords)
+        for (int a = 0; a < dim; ++a) coords[e * dim + a] = pts[i * dim + a] - pts[j * dim + a];
+}
+
+template <bool FILL, typename... A> void launch_neighbour_batched(int dim, int32_t n, hipStream_t st, A... a)
+{
+    if (dim == 1) hipLaunchKernelGGL((rgb_neighbour_kernel<1, FILL>), dim3(blocks(n)), dim3(256), 0, st, n, a...);
+    else if (dim == 2) hipLaunchKernelGGL((rgb_neighbour_kernel<2, FILL>), dim3(blocks(n)), dim3(256), 0, st, n, a...);
+    else hipLaunchKernelGGL((rgb_neighbour_kernel<3, FILL>), dim3(blocks(n)), dim3(256), 0, st, n, a...);
+}
+
+// the checks both batched entries make before anything touches the device: 0, or 2 with the message set
+int batch_arguments_check(const char *who, int32_t B, const int32_t *offsets, int32_t dim, float radius)
+{
+    AMP_REQUIRE(dim >= 1 && dim <= 3, "%s: dim = %d outside [1,3]", who, dim);
+    AMP_REQUIRE(isfinite(radius) && radius > 0.f, "%s: radius = %g is not a positive finite number", who, (double)radius);
+    AMP_REQUIRE(isfinite(radius * radius), "%s: radius = %g squared is not finite in fp32", who, (double)radius);
+    AMP_REQUIRE(B >= 0, "%s: n_clouds = %d is negative", who, B);
+    AMP_REQUIRE(offsets != nullptr, "%s: null offsets", who);
+    AMP_REQUIRE(offsets[0] == 0, "%s: offsets(1) = %d, not 0", who, offsets[0]);
+    for (int32_t b = 0; b < B; ++b)
+        AMP_REQUIRE(offsets[b + 1] >= offsets[b], "%s: cloud %d: offsets descend from %d to %d", who, b + 1, offsets[b], offsets[b + 1]);
+    return 0;
+}
+
+} // namespace
+
+namespace amp {
+
+// pairs_dev / coords_dev both null: count only (edge_offsets_out is filled either way).  Everything on the library's stream;
+// synchronised on return.
+int radius_pairs_batched_core(int32_t B, int32_t n, const int32_t *offsets, int32_t dim, const float *points_dev, float radius,
+                              int32_t *pairs_dev, float *coords_dev, int64_t capacity, int64_t *edge_offsets_out, int64_t *n_pairs_out)
+{
+    static const char who[] = "radius_pairs_batched";
+    AMP_REQUIRE(n_pairs_out != nullptr, "radius_pairs_batched: null n_pairs_out");
+    *n_pairs_out = 0;
+    if (int rc = batch_arguments_check(who, B, offsets, dim, radius)) return rc;
+    AMP_REQUIRE(offsets[B] == n, "radius_pairs_batched: offsets end at %d, the batch has %d points", offsets[B], n);
+    AMP_REQUIRE(n == 0 || points_dev != nullptr, "radius_pairs_batched: null points");
+    if (edge_offsets_out) std::fill(edge_offsets_out, edge_offsets_out + B + 1, (int64_t)0);
+    if (n == 0) return 0;
+    const float r2 = radius * radius;
+    hipStream_t st = stream();
+    const bool fill = pairs_dev != nullptr || coords_dev != nullptr;
+
+    // work items in order of (cloud, first point); item_first[b] = the first item of cloud b or of a later one
+    std::vector<int32_t> items, item_first((size_t)B + 1);
+    int32_t m_max = 0;
+    for (int32_t b = 0; b < B; ++b) {
+        item_first[b] = (int32_t)(items.size() / 3);
+        m_max = std::max(m_max, offsets[b + 1] - offsets[b]);
+        for (int64_t p0 = offsets[b]; p0 < offsets[b + 1]; p0 += kItemPoints)
+            items.insert(items.end(), {b, (int32_t)p0, (int32_t)std::min<int64_t>(p0 + kItemPoints, offsets[b + 1])});
+    }
+    const int32_t W = (int32_t)(items.size() / 3);       // at most B + n / kItemPoints, and only non-empty clouds have one: W <= n
+    item_first[B] = W;
+
+    Scratch tmp;
+    int32_t *d_items = nullptr, *d_item_first = nullptr, *d_off = nullptr;
+    Box *d_partial = nullptr, *d_box = nullptr;
+    if (tmp.get(&d_items, items.size()) || tmp.get(&d_item_first, (size_t)B + 1) || tmp.get(&d_off, (size_t)B + 1) ||
+        tmp.get(&d_partial, W) || tmp.get(&d_box, B))
+        return 1;
+    AMP_HIP(hipMemcpyAsync(d_items, items.data(), sizeof(int32_t) * items.size(), hipMemcpyHostToDevice, st));
+    AMP_HIP(hipMemcpyAsync(d_item_first, item_first.data(), sizeof(int32_t) * ((size_t)B + 1), hipMemcpyHostToDevice, st));
+    AMP_HIP(hipMemcpyAsync(d_off, offsets, sizeof(int32_t) * ((size_t)B + 1), hipMemcpyHostToDevice, st));
+    const unsigned item_blocks = (unsigned)(((int64_t)W + kItemWaves - 1) / kItemWaves);
+    hipLaunchKernelGGL(rgb_box_item_kernel, dim3(item_blocks), dim3(64 * kItemWaves), 0, st, W, (const int32_t *)d_items, (int)dim,
+                       points_dev, d_partial);
+    hipLaunchKernelGGL(rgb_box_cloud_kernel, dim3(blocks(B)), dim3(256), 0, st, B, (const int32_t *)d_item_first, (const Box *)d_partial,
+                       d_box);
+    AMP_LAUNCH_CHECK();
+    std::vector<Box> box((size_t)B);
+    AMP_HIP(hipMemcpyAsync(box.data(), d_box, sizeof(Box) * (size_t)B, hipMemcpyDeviceToHost, st));
+    AMP_HIP(hipStreamSynchronize(st));
+    unsigned long long first_bad = ~0ull;
+    int32_t bad_cloud = 0;
+    for (int32_t b = 0; b < B; ++b)
+        if (box[b].first_bad < first_bad) {
+            first_bad = box[b].first_bad;
+            bad_cloud = b;
+        }
+    if (first_bad != ~0ull) {
+        float p[3] = {0.f, 0.f, 0.f};
+        AMP_HIP(hipMemcpy(p, points_dev + first_bad * (unsigned long long)dim, sizeof(float) * dim, hipMemcpyDeviceToHost));
+        int a = 0;
+        while (a < dim - 1 && isfinite(p[a])) ++a;
+        set_error("radius_pairs_batched: cloud %d: points(%d,%llu) = %g is not finite", bad_cloud + 1, a + 1, first_bad + 1, (double)p[a]);
+        return 2;
+    }
+
+    // a grid per non-empty cloud; cell_base = the exclusive sum of the clouds' cell counts (an empty cloud adds 0)
+    std::vector<Grid> grids((size_t)B);
+    std::vector<uint32_t> cell_base((size_t)B + 1);
+    int64_t total_cells = 0;
+    for (int32_t b = 0; b < B; ++b) {
+        cell_base[b] = (uint32_t)total_cells;
+        const int32_t m = offsets[b + 1] - offsets[b];
+        if (m == 0) {
+            grids[b] = Grid{};
+            continue;
+        }
+        grids[b] = make_grid(box[b], dim, m, radius);
+        total_cells += (int64_t)grids[b].nc[0] * grids[b].nc[1] * grids[b].nc[2];
+        AMP_REQUIRE(total_cells < (int64_t)INT32_MAX, "radius_pairs_batched: more than 2^31 grid cells over %d points", n);
+    }
+    cell_base[B] = (uint32_t)total_cells;
+    const uint32_t n_cells = (uint32_t)total_cells;
+
+    Grid *d_grids = nullptr;
+    uint32_t *d_cell_base = nullptr, *d_key = nullptr, *d_key_s = nullptr, *d_key_t = nullptr, *d_count = nullptr;
+    int32_t *d_perm = nullptr, *d_perm_t = nullptr, *d_cell_start = nullptr;
+    float *d_sorted = nullptr;
+    unsigned long long *d_tile = nullptr, *d_offset = nullptr;
+    long long *d_edge_off = nullptr;
+    void *d_temp = nullptr;
+    const uint32_t tiles = scan64::tiles(n);
+    if (tmp.get(&d_grids, B) || tmp.get(&d_cell_base, (size_t)B + 1) || tmp.get(&d_key, n) || tmp.get(&d_key_s, n) ||
+        tmp.get(&d_key_t, n) || tmp.get(&d_perm, n) || tmp.get(&d_perm_t, n) || tmp.get(&d_cell_start, (size_t)n_cells + 1) ||
+        tmp.get(&d_sorted, (size_t)n * dim) || tmp.get(&d_count, n) || tmp.get(&d_tile, (size_t)tiles + 1) || tmp.get(&d_offset, n) ||
+        tmp.get(&d_edge_off, (size_t)B + 1) || tmp.get((char **)&d_temp, radix::scratch_bytes(n)))
+        return 1;
+    AMP_HIP(hipMemcpyAsync(d_grids, grids.data(), sizeof(Grid) * (size_t)B, hipMemcpyHostToDevice, st));
+    AMP_HIP(hipMemcpyAsync(d_cell_base, cell_base.data(), sizeof(uint32_t) * ((size_t)B + 1), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(rgb_cell_key_kernel, dim3(item_blocks), dim3(64 * kItemWaves), 0, st, W, (const int32_t *)d_items, (int)dim,
+                       points_dev, (const Grid *)d_grids, (const uint32_t *)d_cell_base, d_key);
+    AMP_LAUNCH_CHECK();
+    if (int rc = radix::sort_pairs<uint32_t>((const uint32_t *)d_key, nullptr, n, bits_for(n_cells - 1), d_key_s, d_perm, d_key_t, d_perm_t,
+                                             d_temp, st))
+        return rc;
+    hipLaunchKernelGGL(rg_gather_points_kernel, dim3(blocks(n)), dim3(256), 0, st, n, (int)dim, points_dev, (const int32_t *)d_perm,
+                       d_sorted);
+    hipLaunchKernelGGL(rg_cell_start_kernel, dim3(blocks((int64_t)n_cells + 1)), dim3(256), 0, st, n_cells, (const uint32_t *)d_key_s, n,
+                       d_cell_start);
+    const unsigned long long M = (unsigned long long)m_max;
+    launch_neighbour_batched<false>(dim, n, st, B, (const int32_t *)d_off, (const Grid *)d_grids, (const uint32_t *)d_cell_base, M, r2,
+                                    (const float *)d_sorted, (const int32_t *)d_perm, (const uint32_t *)d_key_s,
+                                    (const int32_t *)d_cell_start, d_count, (const unsigned long long *)nullptr,
+                                    (unsigned long long *)nullptr);
+    hipLaunchKernelGGL(scan64::tile_sum_kernel<uint32_t>, dim3(tiles), dim3(256), 0, st, (int64_t)n, (const uint32_t *)d_count, d_tile);
+    hipLaunchKernelGGL(scan64::scan_tiles_kernel, dim3(1), dim3(256), 0, st, tiles, d_tile);
+    hipLaunchKernelGGL(scan64::apply_kernel<uint32_t>, dim3(tiles), dim3(256), 0, st, (int64_t)n, (const uint32_t *)d_count,
+                       (const unsigned long long *)d_tile, d_offset);
+    hipLaunchKernelGGL(rgb_edge_offsets_kernel, dim3(blocks((int64_t)B + 1)), dim3(256), 0, st, B, n, (const int32_t *)d_off,
+                       (const unsigned long long *)d_offset, (const unsigned long long *)(d_tile + tiles), d_edge_off);
+    AMP_LAUNCH_CHECK();
+    unsigned long long total = 0;
+    AMP_HIP(hipMemcpyAsync(&total, d_tile + tiles, sizeof(total), hipMemcpyDeviceToHost, st));
+    if (edge_offsets_out)
+        AMP_HIP(hipMemcpyAsync(edge_offsets_out, d_edge_off, sizeof(int64_t) * ((size_t)B + 1), hipMemcpyDeviceToHost, st));
+    AMP_HIP(hipStreamSynchronize(st));
+    // the limit of csr_from_edges_core, found by the count pass before anything of that size is allocated
+    AMP_REQUIRE(total < (1ull << 31) && 2 * (int64_t)total + n < (int64_t)INT32_MAX,
+                "radius_pairs_batched: %llu pairs among %d points: more than 2^31 CSR entries", total, n);
+    *n_pairs_out = (int64_t)total;
+    if (!fill) return 0;
+    AMP_REQUIRE(capacity >= (int64_t)total, "radius_pairs_batched: the output buffers hold %lld pairs, the batch has %lld",
+                (long long)capacity, (long long)total);
+    if (total == 0) return 0;
+
+    const int64_t E = (int64_t)total;
+    unsigned long long *d_pk = nullptr, *d_pk_s = nullptr, *d_pk_t = nullptr;
+    int32_t *d_v = nullptr, *d_v_t = nullptr;
+    void *d_temp2 = nullptr;
+    if (tmp.get(&d_pk, E) || tmp.get(&d_pk_s, E) || tmp.get(&d_pk_t, E) || tmp.get(&d_v, E) || tmp.get(&d_v_t, E) ||
+        tmp.get((char **)&d_temp2, radix::scratch_bytes(E)))
+        return 1;
+    launch_neighbour_batched<true>(dim, n, st, B, (const int32_t *)d_off, (const Grid *)d_grids, (const uint32_t *)d_cell_base, M, r2,
+                                   (const float *)d_sorted, (const int32_t *)d_perm, (const uint32_t *)d_key_s,
+                                   (const int32_t *)d_cell_start, (uint32_t *)nullptr, (const unsigned long long *)d_offset, d_pk);
+    AMP_LAUNCH_CHECK();
+    // rows are already in order of i; the sort of the whole key orders the partners inside every row
+    const int key_bits = bits_for((unsigned long long)n * M - 1ull);
+    if (int rc = radix::sort_pairs<unsigned long long>((const unsigned long long *)d_pk, nullptr, E, key_bits, d_pk_s, d_v, d_pk_t, d_v_t,
+                                                       d_temp2, st))
+        return rc;
+    hipLaunchKernelGGL(rgb_emit_kernel, dim3(blocks(E)), dim3(256), 0, st, E, B, (const int32_t *)d_off, M, (int)dim,
+                       (const unsigned long long *)d_pk_s, points_dev, pairs_dev, coords_dev);
+    AMP_LAUNCH_CHECK();
+    AMP_HIP(hipStreamSynchronize(st));   // scratch dies with this scope
+    return 0;
+}
+
+} // namespace amp
+
+extern "C" int athena_mp_radius_pairs_batched(int32_t n_clouds, int32_t n, const int32_t *offsets_host, int32_t dim,
+                                              const float *points_dev, float radius, int32_t *pairs_dev, float *coords_dev,
+                                              int64_t capacity, int64_t *edge_offsets_host, int64_t *n_pairs_out)
+{
+    return amp::radius_pairs_batched_core(n_clouds, n, offsets_host, dim, points_dev, radius, pairs_dev, coords_dev, capacity,
+                                          edge_offsets_host, n_pairs_out);
+}
+
+extern "C" int athena_mp_radius_graph_batched_host(int32_t n_clouds, int32_t n, const int32_t *offsets_host, int32_t dim,
+                                                   const float *points_host, float radius, int32_t add_self_loops, int32_t *adj_ia_out,
+                                                   int32_t *adj_ja_out, int64_t capacity, int64_t *nnz_out, float *coords_out,
+                                                   int64_t coords_capacity, int64_t *n_pairs_out, int64_t *edge_offsets_out)
+{
+    AMP_REQUIRE(nnz_out != nullptr && n_pairs_out != nullptr, "radius_graph_batched_host: null output pointer");
+    *nnz_out = *n_pairs_out = 0;
+    AMP_REQUIRE(n >= 0 && (n == 0 || points_host != nullptr), "radius_graph_batched_host: bad arguments (n = %d)", n);
+    // before the points are uploaded: dim sizes the copy
+    if (int rc = batch_arguments_check("radius_graph_batched_host", n_clouds, offsets_host, dim, radius)) return rc;
+    hipStream_t st = amp::stream();
+    Scratch tmp;
+    float *d_pts = nullptr, *d_coords = nullptr;
+    int32_t *d_pairs = nullptr;
+    if (tmp.get(&d_pts, (size_t)n * dim)) return 1;
+    if (n > 0) AMP_HIP(hipMemcpyAsync(d_pts, points_host, sizeof(float) * (size_t)n * dim, hipMemcpyHostToDevice, st));
+    int64_t E = 0;
+    if (int rc = amp::radius_pairs_batched_core(n_clouds, n, offsets_host, dim, d_pts, radius, nullptr, nullptr, 0, edge_offsets_out, &E))
+        return rc;
+    // no self pair and no duplicate pair: every pair is two entries, every vertex gets its loop when asked
+    const int64_t nnz = 2 * E + (add_self_loops ? n : 0);
+    *n_pairs_out = E;
+    *nnz_out = nnz;
+    if (adj_ja_out == nullptr) return 0;                          // size query
+    AMP_REQUIRE(adj_ia_out != nullptr && (coords_out != nullptr || E == 0), "radius_graph_batched_host: null output array");
+    AMP_REQUIRE(capacity >= nnz, "radius_graph_batched_host: adj_ja buffer holds %lld entries, the graph has %lld", (long long)capacity,
+                (long long)nnz);
+    AMP_REQUIRE(coords_capacity >= E, "radius_graph_batched_host: coords buffer holds %lld pairs, the graph has %lld",
+                (long long)coords_capacity, (long long)E);
+    if (tmp.get(&d_pairs, 2 * (size_t)E) || tmp.get(&d_coords, (size_t)E * dim)) return 1;
+    if (int rc = amp::radius_pairs_batched_core(n_clouds, n, offsets_host, dim, d_pts, radius, d_pairs, d_coords, E, edge_offsets_out, &E))
+        return rc;
+    if (E > 0) AMP_HIP(hipMemcpyAsync(coords_out, d_coords, sizeof(float) * (size_t)E * dim, hipMemcpyDeviceToHost, st));
+    int64_t nnz_built = 0;
+    if (int rc = amp::csr_from_edges_core(n, E, d_pairs, add_self_loops, adj_ia_out, adj_ja_out, capacity, &nnz_built, nullptr, true))
+        return rc;
+    AMP_HIP(hipStreamSynchronize(st));
+    *nnz_out = nnz_built;
+    return 0;
+}

@@ -51,6 +51,7 @@ module athena_mp_c
   public :: athena_mp_kipf_layer_fwd, athena_mp_kipf_layer_bwd_x, athena_mp_activation_bwd
   public :: athena_mp_csr_from_edges, athena_mp_graph_export, athena_mp_graph_create_from_edges
   public :: athena_mp_graph_create_from_edges_dev, athena_mp_radius_pairs, athena_mp_radius_graph_host
+  public :: athena_mp_radius_pairs_batched, athena_mp_radius_graph_batched_host
   public :: athena_mp_periodic_pairs, athena_mp_periodic_graph_host, athena_mp_periodic_stats
   public :: athena_mp_edge_grad_to_points, athena_mp_periodic_grad
   public :: athena_mp_edge_grad_to_points_host, athena_mp_periodic_grad_host
@@ -508,6 +509,34 @@ module athena_mp_c
        real(c_float), intent(in) :: points(dim, *)
        real(c_float), value :: radius
        type(c_ptr), value :: adj_ia, adj_ja, coords     !! c_loc of adj_ia(n+1), adj_ja(2,capacity), coords(dim,coords_capacity)
+       integer(c_int64_t), value :: capacity, coords_capacity
+       integer(c_int64_t), intent(out) :: nnz, n_pairs
+     end function
+     !! a batch of point clouds -> ONE block-diagonal pair list: offsets (n_clouds + 1) on the host, 0-based, ascending from 0 to n;
+     !! points (dim, n) on the device -> pairs (2, capacity) and coords (dim, capacity) on the device, each may be c_null_ptr (both:
+     !! n_pairs and edge_offsets only).  edge_offsets: c_loc of an integer(c_int64_t) (n_clouds + 1) host array, or c_null_ptr
+     !! (definition: include/athena_mp.h)
+     integer(c_int) function athena_mp_radius_pairs_batched(n_clouds, n, offsets, dim, points_dev, radius, pairs_dev, coords_dev, &
+          capacity, edge_offsets, n_pairs) bind(C, name="athena_mp_radius_pairs_batched")
+       import :: c_int, c_int32_t, c_int64_t, c_float, c_ptr
+       integer(c_int32_t), value :: n_clouds, n, dim
+       integer(c_int32_t), intent(in) :: offsets(*)
+       type(c_ptr), value :: points_dev, pairs_dev, coords_dev, edge_offsets
+       real(c_float), value :: radius
+       integer(c_int64_t), value :: capacity
+       integer(c_int64_t), intent(out) :: n_pairs
+     end function
+     !! the same with host arrays: points (dim, n) -> adj_ia (n + 1), adj_ja (2, capacity), coords (dim, coords_capacity),
+     !! edge_offsets (n_clouds + 1); adj_ja = c_null_ptr queries nnz, n_pairs and edge_offsets
+     integer(c_int) function athena_mp_radius_graph_batched_host(n_clouds, n, offsets, dim, points, radius, add_self_loops, &
+          adj_ia, adj_ja, capacity, nnz, coords, coords_capacity, n_pairs, edge_offsets) &
+          bind(C, name="athena_mp_radius_graph_batched_host")
+       import :: c_int, c_int32_t, c_int64_t, c_float, c_ptr
+       integer(c_int32_t), value :: n_clouds, n, dim, add_self_loops
+       integer(c_int32_t), intent(in) :: offsets(*)
+       real(c_float), intent(in) :: points(dim, *)
+       real(c_float), value :: radius
+       type(c_ptr), value :: adj_ia, adj_ja, coords, edge_offsets
        integer(c_int64_t), value :: capacity, coords_capacity
        integer(c_int64_t), intent(out) :: nnz, n_pairs
      end function

@@ -220,6 +220,38 @@ class graph_type:
         self.adj_ia, self.adj_ja = ia, ja
         return coords
 
+    def generate_radius_batch_adjacency_device(self, points, offsets, radius, add_self_loops=False):
+        """The radius graphs of a batch of point clouds as ONE block-diagonal graph, built on the GPU
+        (athena_mp_radius_graph_batched_host; the definition is in include/athena_mp.h): points [n, dim] float32, dim 1..3,
+        offsets [B + 1] 0-based; cloud b is the rows offsets[b] .. offsets[b+1]-1.  Sets num_vertices (when unset), num_edges,
+        adj_ia, adj_ja -- what generate_radius_adjacency_device makes of every cloud, edge ids running over the batch -- and
+        returns (coords [num_edges, dim] = p_i - p_j, edge_offsets [B + 1] int64) as numpy.  The host-array sibling of
+        DeviceGraph.from_point_clouds."""
+        pts = np.ascontiguousarray(points, dtype=np.float32)
+        off = np.ascontiguousarray(offsets, dtype=np.int32)
+        if pts.ndim != 2 or off.ndim != 1 or off.size < 1:
+            raise ValueError("points must be [n, dim] and offsets [B + 1]")
+        n, dim = pts.shape
+        B = off.size - 1
+        if self.num_vertices == 0:
+            self.num_vertices = n
+        if n != self.num_vertices:
+            raise ValueError("points must hold one row per vertex")
+        _capi.init(0)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        nnz, E = C.c_int64(), C.c_int64()
+        head = (B, n, vp(off), dim, vp(pts), float(radius), int(bool(add_self_loops)))
+        _capi.call("athena_mp_radius_graph_batched_host", *head, None, None, 0, C.byref(nnz), None, 0, C.byref(E), None)
+        ia = np.empty(n + 1, np.int32)
+        ja = np.empty((2, nnz.value), np.int32, order="F")
+        coords = np.empty((E.value, dim), np.float32)
+        eoff = np.empty(B + 1, np.int64)
+        _capi.call("athena_mp_radius_graph_batched_host", *head, vp(ia), vp(ja), nnz.value, C.byref(nnz), vp(coords), E.value,
+                   C.byref(E), vp(eoff))
+        self.num_edges = int(E.value)
+        self.adj_ia, self.adj_ja = ia, ja
+        return coords, eoff
+
     def generate_periodic_adjacency_device(self, frac, lat, offsets, cutoff_min, cutoff_max, pbc=(1, 1, 1), add_self_loops=False):
         """The neighbour graphs of a batch of periodic structures as ONE block-diagonal graph, built on the GPU
         (athena_mp_periodic_graph_host; the definition is in include/athena_mp.h): frac [n, 3] float32 fractional coordinates,
@@ -440,6 +472,55 @@ class DeviceGraph:
         if want_adjacency:
             return self, coords, ia, np.asfortranarray(ja[:, :self.nnz])
         return self, coords
+
+    @classmethod
+    def from_point_clouds(cls, points, offsets, radius, add_self_loops=False, want_adjacency=False, device=0):
+        """A batch of point clouds -> one block-diagonal device handle without the pair list leaving HBM
+        (athena_mp_radius_pairs_batched, then athena_mp_graph_create_from_edges_dev): what from_points makes of every cloud, edge
+        ids running over the batch.  points [n, dim] float32, dim 1..3: a numpy array, or a torch tensor already on the device
+        (then only offsets, the clouds' bounding boxes, edge_offsets and adj_ia cross PCIe, unless the adjacency is asked for);
+        offsets [B + 1] 0-based on the host, cloud b = rows offsets[b] .. offsets[b+1]-1, empty clouds allowed; one radius for all.
+        The definition of the pairs (fp32, term by term) is in include/athena_mp.h.  Returns (handle, coords, vertex_offsets,
+        edge_offsets) or, with want_adjacency, (..., adj_ia, adj_ja): coords is a device tensor [num_edges, dim] = p_i - p_j,
+        i < j, rows in edge-id order; vertex_offsets (int32) and edge_offsets (int64) are numpy [B + 1] -- what
+        DeviceDataset(handle, vertex_offsets, edge_offsets) and graph_nop_layer_type.set_graph_handle(handle, vertex_offsets)
+        cut the batch by."""
+        import torch
+
+        _capi.init(device)
+        dev = torch.device("cuda", device)
+        if isinstance(points, torch.Tensor):
+            pts = points.to(dev, torch.float32).contiguous()
+        else:
+            pts = torch.from_numpy(np.ascontiguousarray(points, dtype=np.float32)).to(dev)
+        off = np.ascontiguousarray(offsets, dtype=np.int32)
+        if pts.dim() != 2 or off.ndim != 1 or off.size < 1:
+            raise ValueError("points must be [n, dim] and offsets [B + 1]")
+        n, dim, B = int(pts.shape[0]), int(pts.shape[1]), int(off.size - 1)
+        _capi.use_torch_stream()
+        ptr = lambda t: C.c_void_p(t.data_ptr())
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        E = C.c_int64()
+        eoff = np.empty(B + 1, np.int64)
+        head = (B, n, vp(off), dim, ptr(pts), float(radius))
+        _capi.call("athena_mp_radius_pairs_batched", *head, None, None, 0, vp(eoff), C.byref(E))
+        pairs = torch.empty((E.value, 2), dtype=torch.int32, device=dev)       # the memory of a column-major [2, E]
+        coords = torch.empty((E.value, dim), dtype=torch.float32, device=dev)
+        _capi.call("athena_mp_radius_pairs_batched", *head, ptr(pairs), ptr(coords), E.value, vp(eoff), C.byref(E))
+        self = cls.__new__(cls)
+        ia = np.empty(n + 1, np.int32)
+        nnz = C.c_int64()
+        h = C.c_void_p()
+        ja = np.empty((2, 2 * E.value + n), np.int32, order="F") if want_adjacency else None
+        _capi.call("athena_mp_graph_create_from_edges_dev", n, E.value, ptr(pairs), int(bool(add_self_loops)), 1, vp(ia),
+                   vp(ja) if ja is not None else None, ja.shape[1] if ja is not None else 0, C.byref(nnz), C.byref(h))
+        self.handle = h
+        self.n_rows = self.n_cols = n
+        self.nnz = int(nnz.value)
+        self.n_edge_cols = int(E.value)
+        if want_adjacency:
+            return self, coords, off.copy(), eoff, ia, np.asfortranarray(ja[:, :self.nnz])
+        return self, coords, off.copy(), eoff
 
     @classmethod
     def from_structures(cls, frac, lat, offsets, cutoff_min, cutoff_max, pbc=(1, 1, 1), add_self_loops=False, want_adjacency=False,

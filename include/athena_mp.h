@@ -136,6 +136,38 @@ int athena_mp_radius_pairs(int32_t n, int32_t dim, const float *points_dev, floa
 int athena_mp_radius_graph_host(int32_t n, int32_t dim, const float *points_host, float radius, int32_t add_self_loops,
                                 int32_t *adj_ia_out, int32_t *adj_ja_out, int64_t capacity, int64_t *nnz_out,
                                 float *coords_out, int64_t coords_capacity, int64_t *n_pairs_out);
+/* A batch of point clouds -> ONE block-diagonal radius graph on the device (radius_graph.hip): what a graph-neural-operator
+ * dataset (many meshes, samples of a PDE, molecules without a cell) needs in front of athena_mp_graph_create_from_edges_dev,
+ * athena_mp_batch_plan_create and athena_mp_edge_grad_to_points.
+ *   points [n, dim] fp32 row-major on the device, dim in 1..3; offsets [n_clouds + 1] int32 on the HOST, 0-based,
+ *   0 = offsets[0] <= ... <= offsets[n_clouds] = n: cloud b is the rows offsets[b] .. offsets[b+1]-1, empty clouds are allowed
+ *   anywhere; one radius fp32 > 0 for all clouds.
+ *   Which pairs join: points i < j are joined iff they lie in the same cloud and s <= fl(radius * radius), with
+ *   delta = p_i - p_j per component in fp32 and s = ((d0*d0) + d1*d1) + d2*d2, every multiply and add rounded to fp32 on its own:
+ *   the predicate of athena_mp_radius_pairs, unchanged.  No self pairs; coincident points of one cloud are joined.
+ *   Numbering: pairs are numbered in lexicographic order of the global (i, j); the 1-based rank is the edge id.  pairs
+ *   [2, capacity] column-major, 1-based global indices; coords [capacity, dim], coords[e, :] = p_i - p_j.
+ *   edge_offsets [n_clouds + 1] int64 on the HOST (may be NULL): edge_offsets[b] = the number of pairs whose i is below
+ *   offsets[b]; edge_offsets[n_clouds] = the number of pairs.
+ * Equivalently: the concatenation, in cloud order, of what athena_mp_radius_pairs returns for each slice
+ * points[offsets[b] : offsets[b+1]], with offsets[b] added to both indices.
+ * pairs_dev == NULL && coords_dev == NULL: size query (the count pass only; edge_offsets is still filled).  Either of the two
+ * may be NULL alone.  Refused with a message: dim outside 1..3; a radius that is not finite or <= 0 or whose square is not finite
+ * in fp32; n_clouds < 0; offsets[0] != 0; a descending offset (the cloud is named, 1-based); offsets[n_clouds] != n; a non-finite
+ * coordinate (cloud, component and point of the first one are named, 1-based); 2 * pairs + n >= 2^31 (found by the count pass,
+ * before anything of that size is allocated); capacity < pairs.  The library stays usable after a refusal.  Two builds of the
+ * same input are byte-identical. */
+int athena_mp_radius_pairs_batched(int32_t n_clouds, int32_t n, const int32_t *offsets_host, int32_t dim, const float *points_dev,
+                                   float radius, int32_t *pairs_dev, float *coords_dev, int64_t capacity,
+                                   int64_t *edge_offsets_host, int64_t *n_pairs_out);
+/* The same with every array on the host, for callers that hold Fortran arrays: clouds -> adj_ia [n+1], adj_ja [2, capacity]
+ * column-major (what generate_adjacency [+ add_self_loops] makes of the pair list), coords [coords_capacity, dim] and
+ * edge_offsets [n_clouds + 1] (may be NULL).  adj_ja_out == NULL: size query for both counts (*nnz_out, *n_pairs_out) and
+ * edge_offsets. */
+int athena_mp_radius_graph_batched_host(int32_t n_clouds, int32_t n, const int32_t *offsets_host, int32_t dim,
+                                        const float *points_host, float radius, int32_t add_self_loops, int32_t *adj_ia_out,
+                                        int32_t *adj_ja_out, int64_t capacity, int64_t *nnz_out, float *coords_out,
+                                        int64_t coords_capacity, int64_t *n_pairs_out, int64_t *edge_offsets_out);
 /* Periodic structures -> neighbour graphs on the device, a batch per call (periodic_graph.hip).  It replaces get_graph_from_basis
  * of the reference's chemical examples (example/example_library/src/mod_read_chemical_graphs.f90:196-278); the step in front of
  * athena_mp_graph_create_from_edges_dev.
