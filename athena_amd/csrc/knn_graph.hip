@@ -1,0 +1,589 @@
+// Points -> k-nearest-neighbour graph on the device, one cloud or a batch: the neighbour cap beside the radius graphs of
+// radius_graph.hip, for clouds whose density varies by orders of magnitude (adaptive meshes, boundary layers).  The result is a
+// pair list with edge ids like theirs, so everything downstream takes it as it is.
+//
+// The definition (include/athena_mp.h; every implementation gives the same arrays, tests compare with np.array_equal):
+//   * s(i, j) is the squared distance of athena_mp_radius_pairs: d = p_i - p_j per component, s = ((d0*d0) + d1*d1) + d2*d2, every
+//     operation rounded to fp32 on its own (-ffp-contract=off).  Symmetric bit for bit.
+//   * the candidates of i -- the other points of its cloud, with a finite radius only those with s <= fl(radius * radius) -- are
+//     ordered by the key (s, j); N_k(i) is the first min(k, candidates) of them.
+//   * i < j is an edge iff j in N_k(i) or i in N_k(j) (union), or both (mutual); pairs in lexicographic order of the global (i, j).
+// The key is one 64-bit integer: s is not negative (and never NaN for finite points: an overflow gives +inf, which orders last),
+// so its bit pattern orders as an unsigned integer; it sits above j.
+//
+// How.  GRID: per cloud a bounding box and a uniform grid, cell keys in disjoint ranges per cloud, one stable radix sort of
+// (cell, point), positions in cell order -- the passes of radius_pairs_batched_core (cell_grid.h).  The cell width is free here:
+// about kGridPoints points per cell, at most 2 m cells per cloud and kMaxCellsAxis per axis; an axis of zero extent is one cell.
+// SEARCH: one 64-lane wave per query point, in cell order.  The wave holds its best keys ascending across its lanes (one key per
+// lane; the first k count) and walks the cells around the point's own in shells of growing Chebyshev distance rho, 64 candidates
+// per step.  A ballot against the k-th key skips a step that cannot improve the list; otherwise the step's keys are sorted across
+// the lanes (bitonic, __shfl_xor) and merged into the list (min against the reversed step, then a bitonic merge).  No LDS, no
+// atomics, no scratch.  SYMMETRISE: the n k entries of nbr become keys min * n + max (padding: n * n), one radix sort, the first
+// key of a run is flagged for union and the second for mutual (a pair occurs at most twice), an exclusive scan of the flags
+// (scan64.h) numbers the pairs, one pass emits pairs and coords; edge_offsets[b] = the scan at the first key >= offsets[b] * n.
+//
+// THE RESULT IS DEFINED BY THE KEY ORDER ALONE; the grid decides only how much is examined.  The stop rule and its proof:
+//
+// Cells.  On an axis with nc > 1 cells the cell of p is c = min(floor(q), nc - 1), q = fl(fl(p - lo) * inv_w) (cell_q: the same
+// function gives the sort key and the search its q).  Let x = (p - lo) * inv_w in exact arithmetic with the fp32 inv_w.  Each of
+// the two roundings is within 2^-24 relative (p - lo is a difference, never subnormal-inexact; lo <= p, so q >= 0; a product
+// that underflows is off by 2^-150 at most), so |q - x| <= (2^-23 + 2^-48) x.  make_knn_grid keeps inv_w a normal number with
+// inv_w <= (nc / extent)(1 + 2^-24), so x <= nc (1 + 2^-23) < 2049 and |q - x| < e := 2049 * (2^-23 + 2^-48) < 2^-11.9.
+//
+// After shell rho, every cell within Chebyshev distance rho of the query's cell c is read.  A point j of an unread cell differs
+// from c by more than rho on some axis a WITH nc > 1 (an axis of one cell has no other cell: it is never "beyond").  On that axis
+//   above (exists iff c + rho + 1 <= nc - 1):  c_j >= c + rho + 1, and floor(q_j) >= c_j whether or not j sits in the clamped
+//     last cell, so q_j >= c + rho + 1.  c < nc - 1 is not clamped.  x_j - x_i > (c + rho + 1 - q_i) - 2 e.
+//   below (exists iff c - rho - 1 >= 0):  c_j <= c - rho - 1 < nc - 1 is not clamped, so q_j < c_j + 1 <= c - rho, and
+//     q_i >= floor(q_i) >= c (clamped or not).  x_i - x_j > (q_i - (c - rho)) - 2 e.
+// The kernel forms u = fl(fl(gap) - kMargin) in fp32 with gap one of the two brackets.  Both results are below 2050, where half
+// an ulp is at most 2^-13: the two roundings add at most 2^-12 in absolute terms.  2 e + 2^-12 < 2^-10.9 + 2^-12 < 2^-10 =: kMargin,
+// the margin -- derived, not tuned -- so u <= gap - 2 e whatever the roundings did.  Hence, in exact arithmetic,
+//   |p_i[a] - p_j[a]| > u_exact / inv_w[a] >= u * w_low[a],   w_low[a] = 1 / inv_w[a] rounded DOWN to fp32 (on the host, in double).
+// t = the smallest fl(u * w_low[a]) over the axes and sides that exist; if none exists the shells have covered the cloud's grid.
+//
+// Roundings of s.  With D = |p_i[a] - p_j[a]| exact: d = fl(p_i - p_j) >= D (1 - 2^-24), d*d and the at most two additions of
+// non-negative terms each lose at most 2^-24 relative and are monotone, so s(i, j) >= D^2 (1 - 2^-24)^5 > D^2 (1 - 2^-21.6).
+// bound = fl(fl(t * t) * kShrink), kShrink = 1 - 2^-20.  t <= u w_low (1 + 2^-24), so bound <= (u w_low)^2 (1 + 2^-24)^4 (1 - 2^-20)
+// < (u w_low)^2 (1 - 2^-20.5) < D^2 (1 - 2^-21.6) <= s(i, j).  Underflow: a bound below 2^-100 is replaced by 0 (never stops
+// early), so D^2 > 2^-100 wherever the bound is used and no product above is subnormal.  Overflow: the bound is capped at FLT_MAX,
+// which only weakens it.  t <= 0 gives bound 0.
+//
+// So after shell rho every point of an unread cell has s >= bound, and the search stops when
+//   (1) the list is full and its k-th s is STRICTLY below bound: every unread key (s, j) is above the k-th key whatever j is; or
+//   (2) there is a cap and bound > fl(radius * radius): every unread point fails the cap; or
+//   (3) no axis has an unread side: the shells have covered the cloud's grid.
+// (3) holds at the latest at rho = the largest nc - 1, so the search ends.  What was read was merged by key, so the list is N_k(i).
+//
+// Worst case: with no cap and clusters far apart that hold fewer than k + 1 points each, a query must cross the gap: it visits
+// every cell of its cloud, most of them empty.  Correct and slow; the cap is the remedy.
+#include <float.h>
+#include <math.h>
+
+#include <algorithm>
+
+#include "cell_grid.h"
+#include "common.h"
+#include "radix_sort.h"
+#include "scan64.h"
+
+namespace {
+
+constexpr double kGridPoints = 2.0;          // points per cell the grid aims for -- not measured yet
+constexpr float kMargin = 1.0f / 1024.0f;    // 2^-10: the header's bound on what the computed cell coordinates can hide
+constexpr float kShrink = 1.0f - 0x1p-20f;   // covers the roundings of s and of the bound itself (header)
+constexpr unsigned long long kNoKey = ~0ull;
+constexpr int kQueryWaves = 4;               // query points per 256-thread block
+
+struct WLow {
+    float w[3];                              // 1 / inv_w rounded down, per axis (unused where nc = 1)
+};
+
+// the squared distance of the definition, term by term in fp32 (-ffp-contract=off: no fused multiply-add)
+template <int DIM> __device__ inline float sq_dist(const float *p, const float *q)
+{
+    const float d0 = p[0] - q[0];
+    float s = d0 * d0;
+    if (DIM > 1) {
+        const float d1 = p[1] - q[1];
+        s = s + d1 * d1;
+    }
+    if (DIM > 2) {
+        const float d2 = p[2] - q[2];
+        s = s + d2 * d2;
+    }
+    return s;
+}
+
+__device__ inline unsigned long long key_min(unsigned long long a, unsigned long long b) { return a < b ? a : b; }
+__device__ inline unsigned long long key_max(unsigned long long a, unsigned long long b) { return a < b ? b : a; }
+
+// the 64 keys of a wave, one per lane, ascending by lane
+__device__ inline unsigned long long wave_sort(unsigned long long c, int lane)
+{
+#pragma unroll
+    for (int size = 2; size <= 64; size <<= 1) {
+        const bool up = (lane & size) == 0;                  // the last round (size 64) ascends in every lane
+#pragma unroll
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            const unsigned long long o = __shfl_xor(c, stride, 64);
+            const bool low = (lane & stride) == 0;
+            c = low == up ? key_min(c, o) : key_max(c, o);
+        }
+    }
+    return c;
+}
+
+// list and step both ascending by lane: the 64 smallest keys of the two, ascending by lane
+__device__ inline unsigned long long wave_merge(unsigned long long list, unsigned long long step, int lane)
+{
+    unsigned long long c = key_min(list, __shfl(step, 63 - lane, 64));     // bitonic, and it holds the 64 smallest
+#pragma unroll
+    for (int stride = 32; stride > 0; stride >>= 1) {
+        const unsigned long long o = __shfl_xor(c, stride, 64);
+        c = (lane & stride) == 0 ? key_min(c, o) : key_max(c, o);
+    }
+    return c;
+}
+
+// One wave per slot of the cell order: the point i = perm[slot] against the cells of its cloud, shell by shell (header).
+// nbr[i, 0..k-1] = N_k(i) as 1-based global ids in key order, padded with 0.  stat[0][slot] = candidates read, stat[1][slot] =
+// cells read, stat[2][slot] = the last shell.
+template <int DIM>
+__global__ __launch_bounds__(64 * kQueryWaves) void knn_search_kernel(int32_t n, int32_t B, const int32_t *__restrict__ offsets,
+                                                                      const Grid *__restrict__ grids, const WLow *__restrict__ wlow,
+                                                                      const uint32_t *__restrict__ cell_base, int k, float r2,
+                                                                      const float *__restrict__ sorted, const int32_t *__restrict__ perm,
+                                                                      const int32_t *__restrict__ cell_start, int32_t *__restrict__ nbr,
+                                                                      uint32_t *__restrict__ stat)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t slot = (int64_t)blockIdx.x * kQueryWaves + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (slot >= n) return;                                   // the whole wave
+    const int32_t i = __builtin_amdgcn_readfirstlane(perm[slot]);
+    const int32_t b = __builtin_amdgcn_readfirstlane(cloud_of(B, offsets, i));
+    const Grid g = grids[b];
+    const WLow wl = wlow[b];
+    const uint32_t cb = cell_base[b];
+    float p[3] = {0.f, 0.f, 0.f}, q[3] = {0.f, 0.f, 0.f};
+    int32_t cc[3] = {0, 0, 0}, nc[3] = {1, 1, 1};
+#pragma unroll
+    for (int a = 0; a < DIM; ++a) {
+        p[a] = sorted[slot * DIM + a];
+        nc[a] = __builtin_amdgcn_readfirstlane(g.nc[a]);
+        q[a] = cell_q(p[a], g.lo[a], g.inv_w[a]);
+        cc[a] = __builtin_amdgcn_readfirstlane(cell_coord(p[a], g.lo[a], g.inv_w[a], nc[a]));
+    }
+    const bool capped = r2 < INFINITY;
+
+    unsigned long long list = kNoKey;
+    uint32_t n_cand = 0, n_cells = 0;
+    int rho = 0;
+
+    // the cells x0 .. x1 of grid row (z, y) are consecutive keys: one contiguous run of slots, all of this cloud
+    auto read_run = [&](int z, int y, int x0, int x1) {
+        const uint32_t first = cb + ((uint32_t)z * (uint32_t)nc[1] + (uint32_t)y) * (uint32_t)nc[0] + (uint32_t)x0;
+        const int32_t beg = __builtin_amdgcn_readfirstlane(cell_start[first]);
+        const int32_t end = __builtin_amdgcn_readfirstlane(cell_start[first + (uint32_t)(x1 - x0) + 1u]);
+        n_cells += (uint32_t)(x1 - x0 + 1);
+        n_cand += (uint32_t)(end - beg);
+        for (int32_t m0 = beg; m0 < end; m0 += 64) {
+            const int32_t m = m0 + lane;
+            unsigned long long key = kNoKey;
+            if (m < end) {
+                const int32_t j = perm[m];
+                float pj[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+                for (int a = 0; a < DIM; ++a) pj[a] = sorted[(int64_t)m * DIM + a];
+                const float s = sq_dist<DIM>(p, pj);         // p_i - p_j; symmetric bit for bit
+                if (j != i && s <= r2) key = ((unsigned long long)__float_as_uint(s) << 32) | (unsigned long long)(uint32_t)j;
+            }
+            const unsigned long long kth = __shfl(list, k - 1, 64);
+            if (__ballot(key < kth) == 0ull) continue;       // nothing here enters the first k
+            list = wave_merge(list, wave_sort(key, lane), lane);
+        }
+    };
+
+    for (;; ++rho) {
+        const int z0 = DIM > 2 ? max(cc[2] - rho, 0) : 0, z1 = DIM > 2 ? min(cc[2] + rho, nc[2] - 1) : 0;
+        const int y0 = DIM > 1 ? max(cc[1] - rho, 0) : 0, y1 = DIM > 1 ? min(cc[1] + rho, nc[1] - 1) : 0;
+        const int x0 = max(cc[0] - rho, 0), x1 = min(cc[0] + rho, nc[0] - 1);
+        for (int z = z0; z <= z1; ++z)
+            for (int y = y0; y <= y1; ++y) {
+                const bool face = rho == 0 || (DIM > 2 && abs(z - cc[2]) == rho) || (DIM > 1 && abs(y - cc[1]) == rho);
+                if (face) {
+                    read_run(z, y, x0, x1);                  // the whole row lies in the shell
+                } else {                                     // only its two ends do
+                    if (cc[0] - rho >= 0) read_run(z, y, cc[0] - rho, cc[0] - rho);
+                    if (cc[0] + rho <= nc[0] - 1) read_run(z, y, cc[0] + rho, cc[0] + rho);
+                }
+            }
+        // the stop rule (header): t = the least distance, on one axis, to a cell not yet read
+        float t = INFINITY;
+#pragma unroll
+        for (int a = 0; a < DIM; ++a) {
+            if (nc[a] <= 1) continue;
+            if (cc[a] + rho + 1 <= nc[a] - 1) t = fminf(t, (((float)(cc[a] + rho + 1) - q[a]) - kMargin) * wl.w[a]);
+            if (cc[a] - rho - 1 >= 0) t = fminf(t, ((q[a] - (float)(cc[a] - rho)) - kMargin) * wl.w[a]);
+        }
+        if (t == INFINITY) break;                            // (3) the shells have covered the cloud's grid
+        float bound = t > 0.f ? fminf((t * t) * kShrink, FLT_MAX) : 0.f;
+        if (bound < 0x1p-100f) bound = 0.f;
+        if (capped && bound > r2) break;                     // (2)
+        const uint32_t kth_s = (uint32_t)(__shfl(list, k - 1, 64) >> 32);   // 0xffffffff while the list is short
+        if (kth_s < __float_as_uint(bound)) break;           // (1) strictly below
+    }
+
+    if (lane < k) nbr[(int64_t)i * k + lane] = list != kNoKey ? (int32_t)(uint32_t)list + 1 : 0;
+    if (lane == 0) {
+        stat[slot] = n_cand;
+        stat[(int64_t)n + slot] = n_cells;
+        stat[2 * (int64_t)n + slot] = (uint32_t)rho;
+    }
+}
+
+// stat [3][n] -> out[block] = {sum, sum, max}: block partials, folded on the host in block order
+constexpr int kStatBlocks = 256;
+__global__ __launch_bounds__(256) void knn_stat_kernel(int32_t n, const uint32_t *__restrict__ stat, unsigned long long *__restrict__ out)
+{
+    __shared__ unsigned long long part[3][256];
+    unsigned long long c = 0, v = 0, r = 0;
+    for (int64_t s = (int64_t)blockIdx.x * 256 + threadIdx.x; s < n; s += (int64_t)gridDim.x * 256) {
+        c += stat[s];
+        v += stat[(int64_t)n + s];
+        const unsigned long long x = stat[2 * (int64_t)n + s];
+        r = x > r ? x : r;
+    }
+    part[0][threadIdx.x] = c;
+    part[1][threadIdx.x] = v;
+    part[2][threadIdx.x] = r;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) {
+            part[0][threadIdx.x] += part[0][threadIdx.x + s];
+            part[1][threadIdx.x] += part[1][threadIdx.x + s];
+            part[2][threadIdx.x] = key_max(part[2][threadIdx.x], part[2][threadIdx.x + s]);
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x < 3) out[3 * blockIdx.x + threadIdx.x] = part[threadIdx.x][0];
+}
+
+// ---- symmetrise ---------------------------------------------------------------------------------------------------------------
+// entry e = (i, t) of nbr -> min * n + max, padding -> n * n (above every pair)
+__global__ __launch_bounds__(256) void knn_pair_key_kernel(int64_t T, int32_t n, int k, const int32_t *__restrict__ nbr,
+                                                           unsigned long long *__restrict__ key)
+{
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= T) return;
+    const unsigned long long i = (unsigned long long)(e / k), N = (unsigned long long)n;
+    const int32_t v = nbr[e];
+    const unsigned long long j = (unsigned long long)(v - 1);
+    key[e] = v <= 0 ? N * N : (i < j ? i * N + j : j * N + i);
+}
+
+// union: the first key of a run; mutual: the second (i -> j and j -> i: a pair occurs at most twice)
+__global__ __launch_bounds__(256) void knn_flag_kernel(int64_t T, unsigned long long pad, int mode, const unsigned long long *__restrict__ key,
+                                                       uint8_t *__restrict__ flag)
+{
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= T) return;
+    const unsigned long long v = key[e];
+    const bool repeat = e > 0 && key[e - 1] == v;
+    flag[e] = v != pad && (mode == 0 ? !repeat : repeat);
+}
+
+__global__ __launch_bounds__(256) void knn_emit_kernel(int64_t T, int32_t n, int dim, const unsigned long long *__restrict__ key,
+                                                       const uint8_t *__restrict__ flag, const unsigned long long *__restrict__ offset,
+                                                       const float *__restrict__ pts, int32_t *__restrict__ pairs,
+                                                       float *__restrict__ coords)
+{
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= T || !flag[e]) return;
+    const unsigned long long v = key[e];
+    const int64_t at = (int64_t)offset[e];
+    const int64_t i = (int64_t)(v / (unsigned long long)n), j = (int64_t)(v % (unsigned long long)n);
+    if (pairs) {
+        pairs[2 * at] = (int32_t)i + 1;
+        pairs[2 * at + 1] = (int32_t)j + 1;
+    }
+    if (coords)
+        for (int a = 0; a < dim; ++a) coords[at * dim + a] = pts[i * dim + a] - pts[j * dim + a];
+}
+
+// edge_offsets[b] = pairs whose i is below offsets[b]: the scan at the first key >= offsets[b] * n (b = 0 .. B)
+__global__ __launch_bounds__(256) void knn_edge_offsets_kernel(int32_t B, int32_t n, int64_t T, const int32_t *__restrict__ offsets,
+                                                               const unsigned long long *__restrict__ key,
+                                                               const unsigned long long *__restrict__ offset,
+                                                               const unsigned long long *__restrict__ total,
+                                                               long long *__restrict__ edge_offsets)
+{
+    const int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (b > B) return;
+    const unsigned long long want = (unsigned long long)offsets[b] * (unsigned long long)n;
+    int64_t lo = 0, hi = T;
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if (key[mid] < want) lo = mid + 1; else hi = mid;
+    }
+    edge_offsets[b] = (long long)(lo < T ? offset[lo] : *total);
+}
+
+using amp::Scratch;
+
+float round_down(double v)
+{
+    float f = (float)v;
+    if ((double)f > v) f = nextafterf(f, 0.f);
+    return f;
+}
+
+// About kGridPoints points per cell, at most kMaxCellsAxis cells per axis and 2 m in all.  An axis of zero extent is one cell; so
+// is one whose inv_w would not be a normal fp32 number with the relative accuracy the header's proof uses.
+Grid make_knn_grid(const Box &box, int dim, int32_t m, WLow *wl)
+{
+    Grid g;
+    double extent[3] = {0, 0, 0}, volume = 1.0;
+    int active = 0;
+    for (int a = 0; a < 3; ++a) {
+        g.lo[a] = a < dim ? box.lo[a] : 0.f;
+        g.nc[a] = 1;
+        g.inv_w[a] = 0.f;
+        wl->w[a] = 0.f;
+        if (a < dim) extent[a] = (double)box.hi[a] - (double)box.lo[a];
+        if (extent[a] > 0.0 && extent[a] < 1e37) {
+            volume *= extent[a];
+            ++active;
+        } else {
+            extent[a] = 0.0;
+        }
+    }
+    if (active == 0) return g;
+    const double want = std::max(1.0, (double)m / kGridPoints);
+    const double w = pow(volume / want, 1.0 / active);
+    for (int a = 0; a < 3; ++a) {
+        if (extent[a] == 0.0) continue;
+        const double cells = floor(extent[a] / w);
+        g.nc[a] = !(cells >= 1.0) ? 1 : cells > (double)kMaxCellsAxis ? kMaxCellsAxis : (int32_t)cells;
+    }
+    const int64_t cap = std::min<int64_t>(2 * (int64_t)m, (int64_t)1 << 30);
+    while ((int64_t)g.nc[0] * g.nc[1] * g.nc[2] > cap) {
+        int a = 0;
+        for (int c = 1; c < 3; ++c)
+            if (g.nc[c] > g.nc[a]) a = c;
+        g.nc[a] = (g.nc[a] + 1) / 2;
+    }
+    for (int a = 0; a < 3; ++a) {
+        if (g.nc[a] <= 1) continue;
+        const float inv_w = (float)((double)g.nc[a] / extent[a]);
+        if (!(inv_w >= 1e-30f && inv_w <= 1e30f)) {
+            g.nc[a] = 1;
+            continue;
+        }
+        g.inv_w[a] = inv_w;
+        wl->w[a] = round_down((1.0 / (double)inv_w) * (1.0 - 0x1p-30));
+    }
+    return g;
+}
+
+template <typename... A> void launch_search(int dim, int32_t n, hipStream_t st, A... a)
+{
+    const dim3 grid((unsigned)(((int64_t)n + kQueryWaves - 1) / kQueryWaves)), block(64 * kQueryWaves);
+    if (dim == 1) hipLaunchKernelGGL(knn_search_kernel<1>, grid, block, 0, st, n, a...);
+    else if (dim == 2) hipLaunchKernelGGL(knn_search_kernel<2>, grid, block, 0, st, n, a...);
+    else hipLaunchKernelGGL(knn_search_kernel<3>, grid, block, 0, st, n, a...);
+}
+
+int64_t g_stats[4] = {0, 0, 0, 0};       // athena_mp_knn_stats: of the last call
+
+int knn_arguments_check(const char *who, int32_t B, const int32_t *offsets, int32_t dim, int32_t k, float radius, int32_t mode)
+{
+    AMP_REQUIRE(dim >= 1 && dim <= 3, "%s: dim = %d outside [1,3]", who, dim);
+    AMP_REQUIRE(k >= 1 && k <= 64, "%s: k = %d outside [1,64]", who, k);
+    AMP_REQUIRE(radius > 0.f, "%s: radius = %g is not a positive number (+infinity: no cap)", who, (double)radius);   // NaN fails too
+    AMP_REQUIRE(mode == 0 || mode == 1, "%s: mode = %d is neither 0 (union) nor 1 (mutual)", who, mode);
+    return batch_offsets_check(who, B, offsets);
+}
+
+} // namespace
+
+namespace amp {
+
+// nbr_dev, pairs_dev and coords_dev all null: size query (edge_offsets_out is filled either way).  Everything on the library's
+// stream; synchronised on return.
+int knn_pairs_batched_core(int32_t B, int32_t n, const int32_t *offsets, int32_t dim, const float *points_dev, int32_t k, float radius,
+                           int32_t mode, int32_t *nbr_dev, int32_t *pairs_dev, float *coords_dev, int64_t capacity,
+                           int64_t *edge_offsets_out, int64_t *n_pairs_out)
+{
+    static const char who[] = "knn_pairs_batched";
+    AMP_REQUIRE(n_pairs_out != nullptr, "knn_pairs_batched: null n_pairs_out");
+    *n_pairs_out = 0;
+    std::fill(g_stats, g_stats + 4, (int64_t)0);
+    if (int rc = knn_arguments_check(who, B, offsets, dim, k, radius, mode)) return rc;
+    AMP_REQUIRE(offsets[B] == n, "knn_pairs_batched: offsets end at %d, the batch has %d points", offsets[B], n);
+    AMP_REQUIRE(n == 0 || points_dev != nullptr, "knn_pairs_batched: null points");
+    AMP_REQUIRE((int64_t)n * k < ((int64_t)1 << 31), "knn_pairs_batched: n * k = %lld: more than 2^31 neighbour entries", (long long)n * k);
+    if (edge_offsets_out) std::fill(edge_offsets_out, edge_offsets_out + B + 1, (int64_t)0);
+    if (n == 0) return 0;
+    const float r2 = radius * radius;            // +inf (no cap, or a square beyond fp32): every s passes
+    hipStream_t st = stream();
+    const bool fill = pairs_dev != nullptr || coords_dev != nullptr;
+
+    Scratch tmp;
+    BatchItems it;
+    std::vector<Box> box;
+    if (int rc = batch_boxes(who, B, offsets, dim, points_dev, st, tmp, it, box)) return rc;
+
+    // a grid per non-empty cloud; cell_base = the exclusive sum of the clouds' cell counts (an empty cloud adds 0)
+    std::vector<Grid> grids((size_t)B);
+    std::vector<WLow> wlow((size_t)B);
+    std::vector<uint32_t> cell_base((size_t)B + 1);
+    int64_t total_cells = 0;
+    for (int32_t b = 0; b < B; ++b) {
+        cell_base[b] = (uint32_t)total_cells;
+        const int32_t m = offsets[b + 1] - offsets[b];
+        grids[b] = Grid{};
+        wlow[b] = WLow{};
+        if (m == 0) continue;
+        grids[b] = make_knn_grid(box[b], dim, m, &wlow[b]);
+        total_cells += (int64_t)grids[b].nc[0] * grids[b].nc[1] * grids[b].nc[2];
+        AMP_REQUIRE(total_cells < (int64_t)INT32_MAX, "knn_pairs_batched: more than 2^31 grid cells over %d points", n);
+    }
+    cell_base[B] = (uint32_t)total_cells;
+    const uint32_t n_cells = (uint32_t)total_cells;
+    const int64_t T = (int64_t)n * k;
+
+    Grid *d_grids = nullptr;
+    WLow *d_wlow = nullptr;
+    uint32_t *d_cell_base = nullptr, *d_key = nullptr, *d_key_s = nullptr, *d_key_t = nullptr, *d_stat = nullptr;
+    int32_t *d_perm = nullptr, *d_perm_t = nullptr, *d_cell_start = nullptr, *d_nbr = nullptr;
+    float *d_sorted = nullptr;
+    unsigned long long *d_stat_part = nullptr;
+    void *d_temp = nullptr;
+    if (tmp.get(&d_grids, B) || tmp.get(&d_wlow, B) || tmp.get(&d_cell_base, (size_t)B + 1) || tmp.get(&d_key, n) ||
+        tmp.get(&d_key_s, n) || tmp.get(&d_key_t, n) || tmp.get(&d_perm, n) || tmp.get(&d_perm_t, n) ||
+        tmp.get(&d_cell_start, (size_t)n_cells + 1) || tmp.get(&d_sorted, (size_t)n * dim) || tmp.get(&d_stat, 3 * (size_t)n) ||
+        tmp.get(&d_stat_part, 3 * (size_t)kStatBlocks) || tmp.get((char **)&d_temp, radix::scratch_bytes(n)))
+        return 1;
+    if (nbr_dev == nullptr) {
+        if (tmp.get(&d_nbr, (size_t)T)) return 1;
+    } else {
+        d_nbr = nbr_dev;
+    }
+    AMP_HIP(hipMemcpyAsync(d_grids, grids.data(), sizeof(Grid) * (size_t)B, hipMemcpyHostToDevice, st));
+    AMP_HIP(hipMemcpyAsync(d_wlow, wlow.data(), sizeof(WLow) * (size_t)B, hipMemcpyHostToDevice, st));
+    AMP_HIP(hipMemcpyAsync(d_cell_base, cell_base.data(), sizeof(uint32_t) * ((size_t)B + 1), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(rgb_cell_key_kernel, dim3(it.item_blocks), dim3(64 * kItemWaves), 0, st, it.W, (const int32_t *)it.d_items, (int)dim,
+                       points_dev, (const Grid *)d_grids, (const uint32_t *)d_cell_base, d_key);
+    AMP_LAUNCH_CHECK();
+    if (int rc = radix::sort_pairs<uint32_t>((const uint32_t *)d_key, nullptr, n, bits_for(n_cells - 1), d_key_s, d_perm, d_key_t, d_perm_t,
+                                             d_temp, st))
+        return rc;
+    hipLaunchKernelGGL(rg_gather_points_kernel, dim3(blocks(n)), dim3(256), 0, st, n, (int)dim, points_dev, (const int32_t *)d_perm,
+                       d_sorted);
+    hipLaunchKernelGGL(rg_cell_start_kernel, dim3(blocks((int64_t)n_cells + 1)), dim3(256), 0, st, n_cells, (const uint32_t *)d_key_s, n,
+                       d_cell_start);
+    launch_search(dim, n, st, B, (const int32_t *)it.d_off, (const Grid *)d_grids, (const WLow *)d_wlow, (const uint32_t *)d_cell_base,
+                  (int)k, r2, (const float *)d_sorted, (const int32_t *)d_perm, (const int32_t *)d_cell_start, d_nbr, d_stat);
+    const int stat_blocks = (int)std::min<int64_t>(kStatBlocks, blocks(n));
+    hipLaunchKernelGGL(knn_stat_kernel, dim3(stat_blocks), dim3(256), 0, st, n, (const uint32_t *)d_stat, d_stat_part);
+    AMP_LAUNCH_CHECK();
+
+    // symmetrise: one sort of the n k keys, flags, a 64-bit scan in key order
+    unsigned long long *d_pk = nullptr, *d_pk_s = nullptr, *d_pk_t = nullptr, *d_tile = nullptr, *d_offset = nullptr;
+    int32_t *d_v = nullptr, *d_v_t = nullptr;
+    uint8_t *d_flag = nullptr;
+    long long *d_edge_off = nullptr;
+    void *d_temp2 = nullptr;
+    const uint32_t tiles = scan64::tiles(T);
+    if (tmp.get(&d_pk, T) || tmp.get(&d_pk_s, T) || tmp.get(&d_pk_t, T) || tmp.get(&d_v, T) || tmp.get(&d_v_t, T) || tmp.get(&d_flag, T) ||
+        tmp.get(&d_tile, (size_t)tiles + 1) || tmp.get(&d_offset, T) || tmp.get(&d_edge_off, (size_t)B + 1) ||
+        tmp.get((char **)&d_temp2, radix::scratch_bytes(T)))
+        return 1;
+    const unsigned long long pad = (unsigned long long)n * (unsigned long long)n;
+    hipLaunchKernelGGL(knn_pair_key_kernel, dim3(blocks(T)), dim3(256), 0, st, T, n, (int)k, (const int32_t *)d_nbr, d_pk);
+    AMP_LAUNCH_CHECK();
+    if (int rc = radix::sort_pairs<unsigned long long>((const unsigned long long *)d_pk, nullptr, T, bits_for(pad), d_pk_s, d_v, d_pk_t, d_v_t,
+                                                       d_temp2, st))
+        return rc;
+    hipLaunchKernelGGL(knn_flag_kernel, dim3(blocks(T)), dim3(256), 0, st, T, pad, (int)mode, (const unsigned long long *)d_pk_s, d_flag);
+    hipLaunchKernelGGL(scan64::tile_sum_kernel<uint8_t>, dim3(tiles), dim3(256), 0, st, T, (const uint8_t *)d_flag, d_tile);
+    hipLaunchKernelGGL(scan64::scan_tiles_kernel, dim3(1), dim3(256), 0, st, tiles, d_tile);
+    hipLaunchKernelGGL(scan64::apply_kernel<uint8_t>, dim3(tiles), dim3(256), 0, st, T, (const uint8_t *)d_flag,
+                       (const unsigned long long *)d_tile, d_offset);
+    hipLaunchKernelGGL(knn_edge_offsets_kernel, dim3(blocks((int64_t)B + 1)), dim3(256), 0, st, B, n, T, (const int32_t *)it.d_off,
+                       (const unsigned long long *)d_pk_s, (const unsigned long long *)d_offset,
+                       (const unsigned long long *)(d_tile + tiles), d_edge_off);
+    AMP_LAUNCH_CHECK();
+    unsigned long long total = 0, stat_part[3 * kStatBlocks];
+    AMP_HIP(hipMemcpyAsync(&total, d_tile + tiles, sizeof(total), hipMemcpyDeviceToHost, st));
+    AMP_HIP(hipMemcpyAsync(stat_part, d_stat_part, sizeof(unsigned long long) * 3 * (size_t)stat_blocks, hipMemcpyDeviceToHost, st));
+    if (edge_offsets_out)
+        AMP_HIP(hipMemcpyAsync(edge_offsets_out, d_edge_off, sizeof(int64_t) * ((size_t)B + 1), hipMemcpyDeviceToHost, st));
+    AMP_HIP(hipStreamSynchronize(st));
+    g_stats[0] = n;
+    for (int s = 0; s < stat_blocks; ++s) {
+        g_stats[1] += (int64_t)stat_part[3 * s];
+        g_stats[2] += (int64_t)stat_part[3 * s + 1];
+        g_stats[3] = std::max(g_stats[3], (int64_t)stat_part[3 * s + 2]);
+    }
+    *n_pairs_out = (int64_t)total;
+    if (!fill) return 0;
+    AMP_REQUIRE(capacity >= (int64_t)total, "knn_pairs_batched: the output buffers hold %lld pairs, the graph has %lld", (long long)capacity,
+                (long long)total);
+    if (total == 0) return 0;
+    hipLaunchKernelGGL(knn_emit_kernel, dim3(blocks(T)), dim3(256), 0, st, T, n, (int)dim, (const unsigned long long *)d_pk_s,
+                       (const uint8_t *)d_flag, (const unsigned long long *)d_offset, points_dev, pairs_dev, coords_dev);
+    AMP_LAUNCH_CHECK();
+    AMP_HIP(hipStreamSynchronize(st));   // scratch dies with this scope
+    return 0;
+}
+
+} // namespace amp
+
+extern "C" int athena_mp_knn_pairs_batched(int32_t n_clouds, int32_t n, const int32_t *offsets_host, int32_t dim, const float *points_dev,
+                                           int32_t k, float radius, int32_t mode, int32_t *nbr_dev, int32_t *pairs_dev, float *coords_dev,
+                                           int64_t capacity, int64_t *edge_offsets_host, int64_t *n_pairs_out)
+{
+    return amp::knn_pairs_batched_core(n_clouds, n, offsets_host, dim, points_dev, k, radius, mode, nbr_dev, pairs_dev, coords_dev,
+                                       capacity, edge_offsets_host, n_pairs_out);
+}
+
+extern "C" int athena_mp_knn_pairs(int32_t n, int32_t dim, const float *points_dev, int32_t k, float radius, int32_t mode,
+                                   int32_t *nbr_dev, int32_t *pairs_dev, float *coords_dev, int64_t capacity, int64_t *n_pairs_out)
+{
+    AMP_REQUIRE(n >= 0, "knn_pairs: n = %d is negative", n);
+    const int32_t offsets[2] = {0, n};
+    return amp::knn_pairs_batched_core(1, n, offsets, dim, points_dev, k, radius, mode, nbr_dev, pairs_dev, coords_dev, capacity, nullptr,
+                                       n_pairs_out);
+}
+
+extern "C" int athena_mp_knn_stats(int64_t out[4])
+{
+    AMP_REQUIRE(out != nullptr, "knn_stats: null output");
+    std::copy(g_stats, g_stats + 4, out);
+    return 0;
+}
+
+extern "C" int athena_mp_knn_graph_batched_host(int32_t n_clouds, int32_t n, const int32_t *offsets_host, int32_t dim,
+                                                const float *points_host, int32_t k, float radius, int32_t mode, int32_t add_self_loops,
+                                                int32_t *adj_ia_out, int32_t *adj_ja_out, int64_t capacity, int64_t *nnz_out,
+                                                float *coords_out, int64_t coords_capacity, int64_t *n_pairs_out,
+                                                int64_t *edge_offsets_out)
+{
+    AMP_REQUIRE(nnz_out != nullptr && n_pairs_out != nullptr, "knn_graph_batched_host: null output pointer");
+    *nnz_out = *n_pairs_out = 0;
+    AMP_REQUIRE(n >= 0 && (n == 0 || points_host != nullptr), "knn_graph_batched_host: bad arguments (n = %d)", n);
+    // before the points are uploaded: dim sizes the copy, n * k the buffers
+    if (int rc = knn_arguments_check("knn_graph_batched_host", n_clouds, offsets_host, dim, k, radius, mode)) return rc;
+    AMP_REQUIRE((int64_t)n * k < ((int64_t)1 << 31), "knn_graph_batched_host: n * k = %lld: more than 2^31 neighbour entries",
+                (long long)n * k);
+    hipStream_t st = amp::stream();
+    Scratch tmp;
+    float *d_pts = nullptr, *d_coords = nullptr;
+    int32_t *d_pairs = nullptr;
+    const int64_t T = (int64_t)n * k;            // always enough: one search, narrowed afterwards
+    if (tmp.get(&d_pts, (size_t)n * dim) || tmp.get(&d_pairs, 2 * (size_t)T) || tmp.get(&d_coords, (size_t)T * dim)) return 1;
+    if (n > 0) AMP_HIP(hipMemcpyAsync(d_pts, points_host, sizeof(float) * (size_t)n * dim, hipMemcpyHostToDevice, st));
+    int64_t E = 0;
+    if (int rc = amp::knn_pairs_batched_core(n_clouds, n, offsets_host, dim, d_pts, k, radius, mode, nullptr, d_pairs, d_coords, T,
+                                             edge_offsets_out, &E))
+        return rc;
+    // no self pair and no duplicate pair: every pair is two entries, every vertex gets its loop when asked
+    const int64_t nnz = 2 * E + (add_self_loops ? n : 0);
+    *n_pairs_out = E;
+    *nnz_out = nnz;
+    if (adj_ja_out == nullptr) return 0;                          // size query
+    AMP_REQUIRE(adj_ia_out != nullptr && (coords_out != nullptr || E == 0), "knn_graph_batched_host: null output array");
+    AMP_REQUIRE(capacity >= nnz, "knn_graph_batched_host: adj_ja buffer holds %lld entries, the graph has %lld", (long long)capacity,
+                (long long)nnz);
+    AMP_REQUIRE(coords_capacity >= E, "knn_graph_batched_host: coords buffer holds %lld pairs, the graph has %lld",
+                (long long)coords_capacity, (long long)E);
+    if (E > 0) AMP_HIP(hipMemcpyAsync(coords_out, d_coords, sizeof(float) * (size_t)E * dim, hipMemcpyDeviceToHost, st));
+    int64_t nnz_built = 0;
+    if (int rc = amp::csr_from_edges_core(n, E, d_pairs, add_self_loops, adj_ia_out, adj_ja_out, capacity, &nnz_built, nullptr, true))
+        return rc;
+    AMP_HIP(hipStreamSynchronize(st));
+    *nnz_out = nnz_built;
+    return 0;
+}

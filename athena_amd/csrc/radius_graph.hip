@@ -8,7 +8,8 @@
 //     pairs; two points at the same place are joined.
 //   * pairs are numbered in lexicographic order of (i, j), i < j; coords[e, :] = p_i - p_j (smaller index minus larger).
 //
-// How: a uniform grid whose cells are at least radius * (1 + 2^-10) wide on every axis, at most kMaxCellsAxis cells per axis and
+// How: a uniform grid (its passes are in cell_grid.h, shared with knn_graph.hip) whose cells are at least radius * (1 + 2^-10)
+// wide on every axis, at most kMaxCellsAxis cells per axis and
 // at most 2 n cells in all; a stable radix sort of (cell, point id) (radix_sort.h), the positions copied into cell order; a COUNT
 // pass in which every point counts its partners with a larger id in the 3^dim cells around it; an exclusive scan of the counts
 // IN POINT-ID ORDER (64-bit offsets, scan64.h), so the rows of the pair list already sit in lexicographic order of i; a FILL pass that
@@ -25,127 +26,15 @@
 
 #include <algorithm>
 
+#include "cell_grid.h"
 #include "common.h"
 #include "radix_sort.h"
 #include "scan64.h"
 
 namespace {
 
-constexpr int kMaxCellsAxis = 2048;
 constexpr double kCellMargin = 1.0 / 1024.0;
 constexpr int kBoxBlocks = 512;
-
-struct Box {
-    float lo[3], hi[3];
-    unsigned long long first_bad;   // smallest index of a point with a non-finite coordinate, ~0 if none
-};
-
-struct Grid {
-    float lo[3], inv_w[3];
-    int32_t nc[3];
-};
-
-// ---- bounding box + validity: block partials, then one block folds them in block order -------------------------------------
-__device__ inline void box_fold(Box &a, const Box &b)
-{
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        a.lo[k] = fminf(a.lo[k], b.lo[k]);
-        a.hi[k] = fmaxf(a.hi[k], b.hi[k]);
-    }
-    a.first_bad = b.first_bad < a.first_bad ? b.first_bad : a.first_bad;
-}
-
-__device__ inline Box box_block_reduce(Box b)
-{
-    __shared__ Box part[256];
-    part[threadIdx.x] = b;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) box_fold(part[threadIdx.x], part[threadIdx.x + s]);
-        __syncthreads();
-    }
-    return part[0];
-}
-
-__device__ inline Box box_empty()
-{
-    Box b;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        b.lo[k] = INFINITY;
-        b.hi[k] = -INFINITY;
-    }
-    b.first_bad = ~0ull;
-    return b;
-}
-
-__global__ __launch_bounds__(256) void rg_box_kernel(int32_t n, int dim, const float *__restrict__ pts, Box *__restrict__ partial)
-{
-    Box b = box_empty();
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        bool ok = true;
-        for (int k = 0; k < dim; ++k) {
-            const float v = pts[i * dim + k];
-            ok = ok && isfinite(v);
-            b.lo[k] = fminf(b.lo[k], v);
-            b.hi[k] = fmaxf(b.hi[k], v);
-        }
-        if (!ok && (unsigned long long)i < b.first_bad) b.first_bad = (unsigned long long)i;
-    }
-    b = box_block_reduce(b);
-    if (threadIdx.x == 0) partial[blockIdx.x] = b;
-}
-
-__global__ __launch_bounds__(256) void rg_box_final_kernel(int n_partial, const Box *__restrict__ partial, Box *__restrict__ out)
-{
-    Box b = box_empty();
-    for (int i = threadIdx.x; i < n_partial; i += 256) box_fold(b, partial[i]);
-    b = box_block_reduce(b);
-    if (threadIdx.x == 0) *out = b;
-}
-
-// ---- grid ------------------------------------------------------------------------------------------------------------------
-__device__ inline int32_t cell_coord(float p, float lo, float inv_w, int32_t nc)
-{
-    const float q = (p - lo) * inv_w;
-    const int32_t c = (int32_t)q;             // q >= 0 and finite: truncation is floor
-    return c < nc - 1 ? c : nc - 1;
-}
-
-__global__ __launch_bounds__(256) void rg_cell_key_kernel(int32_t n, int dim, const float *__restrict__ pts, Grid g,
-                                                          uint32_t *__restrict__ key)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    uint32_t c = 0;
-    for (int k = dim - 1; k >= 0; --k) c = c * (uint32_t)g.nc[k] + (uint32_t)cell_coord(pts[i * dim + k], g.lo[k], g.inv_w[k], g.nc[k]);
-    key[i] = c;
-}
-
-// positions in cell order: a cell's points are one contiguous read
-__global__ __launch_bounds__(256) void rg_gather_points_kernel(int32_t n, int dim, const float *__restrict__ pts,
-                                                               const int32_t *__restrict__ perm, float *__restrict__ sorted)
-{
-    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (k >= n) return;
-    const int64_t i = perm[k];
-    for (int a = 0; a < dim; ++a) sorted[k * dim + a] = pts[i * dim + a];
-}
-
-// cell_start[c] = first slot whose sorted key is >= c  (c = 0 .. n_cells)
-__global__ __launch_bounds__(256) void rg_cell_start_kernel(uint32_t n_cells, const uint32_t *__restrict__ sorted_key, int32_t n,
-                                                            int32_t *__restrict__ cell_start)
-{
-    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (c > (int64_t)n_cells) return;
-    int32_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int32_t mid = lo + ((hi - lo) >> 1);
-        if ((int64_t)sorted_key[mid] < c) lo = mid + 1; else hi = mid;
-    }
-    cell_start[c] = lo;
-}
 
 // ---- the predicate, term by term in fp32 (-ffp-contract=off: no fused multiply-add) --------------------------------------------
 template <int DIM> __device__ inline bool joined(const float *__restrict__ a, const float *__restrict__ b, float r2)
@@ -223,14 +112,6 @@ __global__ __launch_bounds__(256) void rg_emit_kernel(int64_t E, int32_t n, int 
     }
     if (coords)
         for (int a = 0; a < dim; ++a) coords[e * dim + a] = pts[i * dim + a] - pts[j * dim + a];
-}
-
-inline unsigned blocks(int64_t n) { return (unsigned)((n + 255) / 256); }
-inline int bits_for(unsigned long long max_value)
-{
-    int b = 1;
-    while (b < 64 && (max_value >> b)) ++b;
-    return b;
 }
 
 using amp::Scratch;
@@ -430,90 +311,6 @@ extern "C" int athena_mp_radius_graph_host(int32_t n, int32_t dim, const float *
 // (i, j), in fewer bits than i * n + j.  No atomics on data; every access to points and coords is 4 bytes wide.
 namespace {
 
-constexpr int kItemPoints = 4096;
-constexpr int kItemWaves = 4;        // work items per 256-thread block
-
-__device__ inline Box box_wave_reduce(Box b)
-{
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-        Box o;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            o.lo[k] = __shfl_xor(b.lo[k], d, 64);
-            o.hi[k] = __shfl_xor(b.hi[k], d, 64);
-        }
-        o.first_bad = __shfl_xor(b.first_bad, d, 64);
-        box_fold(b, o);
-    }
-    return b;
-}
-
-// one wave per work item (cloud, p0, p1): the box and the first non-finite point of points p0 .. p1-1 -> partial[item]
-__global__ __launch_bounds__(64 * kItemWaves) void rgb_box_item_kernel(int32_t n_items, const int32_t *__restrict__ items, int dim,
-                                                                       const float *__restrict__ pts, Box *__restrict__ partial)
-{
-    const int lane = threadIdx.x & 63;
-    const int64_t w = (int64_t)blockIdx.x * kItemWaves + (threadIdx.x >> 6);
-    if (w >= n_items) return;
-    const int32_t p0 = items[3 * w + 1], p1 = items[3 * w + 2];
-    Box b = box_empty();
-    for (int64_t i = (int64_t)p0 + lane; i < p1; i += 64) {
-        bool ok = true;
-        for (int k = 0; k < dim; ++k) {
-            const float v = pts[i * dim + k];
-            ok = ok && isfinite(v);
-            b.lo[k] = fminf(b.lo[k], v);
-            b.hi[k] = fmaxf(b.hi[k], v);
-        }
-        if (!ok && (unsigned long long)i < b.first_bad) b.first_bad = (unsigned long long)i;
-    }
-    b = box_wave_reduce(b);
-    if (lane == 0) partial[w] = b;
-}
-
-// one thread per cloud: its items' partials in item order (an empty cloud has no item: the empty box).  first_bad stays per
-// cloud; the host, which reads every box anyway, takes the smallest
-__global__ __launch_bounds__(256) void rgb_box_cloud_kernel(int32_t B, const int32_t *__restrict__ item_first,
-                                                            const Box *__restrict__ partial, Box *__restrict__ out)
-{
-    const int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (b >= B) return;
-    Box x = box_empty();
-    for (int32_t w = item_first[b]; w < item_first[b + 1]; ++w) box_fold(x, partial[w]);
-    out[b] = x;
-}
-
-// one wave per work item, so the cloud is known without a search: key = cell_base[cloud] + the cell in the cloud's own grid
-__global__ __launch_bounds__(64 * kItemWaves) void rgb_cell_key_kernel(int32_t n_items, const int32_t *__restrict__ items, int dim,
-                                                                       const float *__restrict__ pts, const Grid *__restrict__ grids,
-                                                                       const uint32_t *__restrict__ cell_base, uint32_t *__restrict__ key)
-{
-    const int lane = threadIdx.x & 63;
-    const int64_t w = (int64_t)blockIdx.x * kItemWaves + (threadIdx.x >> 6);
-    if (w >= n_items) return;
-    const int32_t b = items[3 * w], p0 = items[3 * w + 1], p1 = items[3 * w + 2];
-    const Grid g = grids[b];
-    const uint32_t base = cell_base[b];
-    for (int64_t i = (int64_t)p0 + lane; i < p1; i += 64) {
-        uint32_t c = 0;
-        for (int k = dim - 1; k >= 0; --k)
-            c = c * (uint32_t)g.nc[k] + (uint32_t)cell_coord(pts[i * dim + k], g.lo[k], g.inv_w[k], g.nc[k]);
-        key[i] = base + c;
-    }
-}
-
-// the cloud of point i, 0 <= i < offsets[B]: the last b with offsets[b] <= i (empty clouds repeat a value and own no point)
-__device__ inline int32_t cloud_of(int32_t B, const int32_t *__restrict__ offsets, int32_t i)
-{
-    int32_t lo = 0, hi = B;                       // offsets[lo] <= i < offsets[hi]
-    while (hi - lo > 1) {
-        const int32_t mid = lo + ((hi - lo) >> 1);
-        if (offsets[mid] <= i) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 // rg_neighbour_kernel with the grid of the slot's cloud and the walk inside that cloud's cells.
 // FILL = true: key[offset[i] + t] = i * M + (j - offsets[cloud]) for the t-th partner found.
 template <int DIM, bool FILL>
@@ -608,12 +405,7 @@ int batch_arguments_check(const char *who, int32_t B, const int32_t *offsets, in
     AMP_REQUIRE(dim >= 1 && dim <= 3, "%s: dim = %d outside [1,3]", who, dim);
     AMP_REQUIRE(isfinite(radius) && radius > 0.f, "%s: radius = %g is not a positive finite number", who, (double)radius);
     AMP_REQUIRE(isfinite(radius * radius), "%s: radius = %g squared is not finite in fp32", who, (double)radius);
-    AMP_REQUIRE(B >= 0, "%s: n_clouds = %d is negative", who, B);
-    AMP_REQUIRE(offsets != nullptr, "%s: null offsets", who);
-    AMP_REQUIRE(offsets[0] == 0, "%s: offsets(1) = %d, not 0", who, offsets[0]);
-    for (int32_t b = 0; b < B; ++b)
-        AMP_REQUIRE(offsets[b + 1] >= offsets[b], "%s: cloud %d: offsets descend from %d to %d", who, b + 1, offsets[b], offsets[b + 1]);
-    return 0;
+    return batch_offsets_check(who, B, offsets);
 }
 
 } // namespace
@@ -637,51 +429,13 @@ int radius_pairs_batched_core(int32_t B, int32_t n, const int32_t *offsets, int3
     hipStream_t st = stream();
     const bool fill = pairs_dev != nullptr || coords_dev != nullptr;
 
-    // work items in order of (cloud, first point); item_first[b] = the first item of cloud b or of a later one
-    std::vector<int32_t> items, item_first((size_t)B + 1);
-    int32_t m_max = 0;
-    for (int32_t b = 0; b < B; ++b) {
-        item_first[b] = (int32_t)(items.size() / 3);
-        m_max = std::max(m_max, offsets[b + 1] - offsets[b]);
-        for (int64_t p0 = offsets[b]; p0 < offsets[b + 1]; p0 += kItemPoints)
-            items.insert(items.end(), {b, (int32_t)p0, (int32_t)std::min<int64_t>(p0 + kItemPoints, offsets[b + 1])});
-    }
-    const int32_t W = (int32_t)(items.size() / 3);       // at most B + n / kItemPoints, and only non-empty clouds have one: W <= n
-    item_first[B] = W;
-
     Scratch tmp;
-    int32_t *d_items = nullptr, *d_item_first = nullptr, *d_off = nullptr;
-    Box *d_partial = nullptr, *d_box = nullptr;
-    if (tmp.get(&d_items, items.size()) || tmp.get(&d_item_first, (size_t)B + 1) || tmp.get(&d_off, (size_t)B + 1) ||
-        tmp.get(&d_partial, W) || tmp.get(&d_box, B))
-        return 1;
-    AMP_HIP(hipMemcpyAsync(d_items, items.data(), sizeof(int32_t) * items.size(), hipMemcpyHostToDevice, st));
-    AMP_HIP(hipMemcpyAsync(d_item_first, item_first.data(), sizeof(int32_t) * ((size_t)B + 1), hipMemcpyHostToDevice, st));
-    AMP_HIP(hipMemcpyAsync(d_off, offsets, sizeof(int32_t) * ((size_t)B + 1), hipMemcpyHostToDevice, st));
-    const unsigned item_blocks = (unsigned)(((int64_t)W + kItemWaves - 1) / kItemWaves);
-    hipLaunchKernelGGL(rgb_box_item_kernel, dim3(item_blocks), dim3(64 * kItemWaves), 0, st, W, (const int32_t *)d_items, (int)dim,
-                       points_dev, d_partial);
-    hipLaunchKernelGGL(rgb_box_cloud_kernel, dim3(blocks(B)), dim3(256), 0, st, B, (const int32_t *)d_item_first, (const Box *)d_partial,
-                       d_box);
-    AMP_LAUNCH_CHECK();
-    std::vector<Box> box((size_t)B);
-    AMP_HIP(hipMemcpyAsync(box.data(), d_box, sizeof(Box) * (size_t)B, hipMemcpyDeviceToHost, st));
-    AMP_HIP(hipStreamSynchronize(st));
-    unsigned long long first_bad = ~0ull;
-    int32_t bad_cloud = 0;
-    for (int32_t b = 0; b < B; ++b)
-        if (box[b].first_bad < first_bad) {
-            first_bad = box[b].first_bad;
-            bad_cloud = b;
-        }
-    if (first_bad != ~0ull) {
-        float p[3] = {0.f, 0.f, 0.f};
-        AMP_HIP(hipMemcpy(p, points_dev + first_bad * (unsigned long long)dim, sizeof(float) * dim, hipMemcpyDeviceToHost));
-        int a = 0;
-        while (a < dim - 1 && isfinite(p[a])) ++a;
-        set_error("radius_pairs_batched: cloud %d: points(%d,%llu) = %g is not finite", bad_cloud + 1, a + 1, first_bad + 1, (double)p[a]);
-        return 2;
-    }
+    BatchItems it;
+    std::vector<Box> box;
+    if (int rc = batch_boxes(who, B, offsets, dim, points_dev, st, tmp, it, box)) return rc;
+    const int32_t W = it.W, m_max = it.m_max;
+    const int32_t *d_items = it.d_items, *d_off = it.d_off;
+    const unsigned item_blocks = it.item_blocks;
 
     // a grid per non-empty cloud; cell_base = the exclusive sum of the clouds' cell counts (an empty cloud adds 0)
     std::vector<Grid> grids((size_t)B);

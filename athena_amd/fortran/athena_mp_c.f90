@@ -52,6 +52,7 @@ module athena_mp_c
   public :: athena_mp_csr_from_edges, athena_mp_graph_export, athena_mp_graph_create_from_edges
   public :: athena_mp_graph_create_from_edges_dev, athena_mp_radius_pairs, athena_mp_radius_graph_host
   public :: athena_mp_radius_pairs_batched, athena_mp_radius_graph_batched_host
+  public :: athena_mp_knn_pairs_batched, athena_mp_knn_pairs, athena_mp_knn_graph_batched_host, athena_mp_knn_stats
   public :: athena_mp_periodic_pairs, athena_mp_periodic_graph_host, athena_mp_periodic_stats
   public :: athena_mp_edge_grad_to_points, athena_mp_periodic_grad
   public :: athena_mp_edge_grad_to_points_host, athena_mp_periodic_grad_host
@@ -539,6 +540,49 @@ module athena_mp_c
        type(c_ptr), value :: adj_ia, adj_ja, coords, edge_offsets
        integer(c_int64_t), value :: capacity, coords_capacity
        integer(c_int64_t), intent(out) :: nnz, n_pairs
+     end function
+     !! a batch of point clouds -> ONE block-diagonal k-nearest-neighbour pair list (definition: include/athena_mp.h): the first k
+     !! others of every point in the order (squared distance, index), inside radius when it is finite (ieee +infinity: no cap);
+     !! mode 0 = union, 1 = mutual.  nbr (k, n), pairs (2, capacity), coords (dim, capacity) on the device, each may be
+     !! c_null_ptr (all three: n_pairs and edge_offsets only); capacity = n * k always suffices
+     integer(c_int) function athena_mp_knn_pairs_batched(n_clouds, n, offsets, dim, points_dev, k, radius, mode, nbr_dev, pairs_dev, &
+          coords_dev, capacity, edge_offsets, n_pairs) bind(C, name="athena_mp_knn_pairs_batched")
+       import :: c_int, c_int32_t, c_int64_t, c_float, c_ptr
+       integer(c_int32_t), value :: n_clouds, n, dim, k, mode
+       integer(c_int32_t), intent(in) :: offsets(*)
+       type(c_ptr), value :: points_dev, nbr_dev, pairs_dev, coords_dev, edge_offsets
+       real(c_float), value :: radius
+       integer(c_int64_t), value :: capacity
+       integer(c_int64_t), intent(out) :: n_pairs
+     end function
+     !! the same for one cloud
+     integer(c_int) function athena_mp_knn_pairs(n, dim, points_dev, k, radius, mode, nbr_dev, pairs_dev, coords_dev, capacity, &
+          n_pairs) bind(C, name="athena_mp_knn_pairs")
+       import :: c_int, c_int32_t, c_int64_t, c_float, c_ptr
+       integer(c_int32_t), value :: n, dim, k, mode
+       type(c_ptr), value :: points_dev, nbr_dev, pairs_dev, coords_dev
+       real(c_float), value :: radius
+       integer(c_int64_t), value :: capacity
+       integer(c_int64_t), intent(out) :: n_pairs
+     end function
+     !! the same with host arrays: points (dim, n) -> adj_ia (n + 1), adj_ja (2, capacity), coords (dim, coords_capacity),
+     !! edge_offsets (n_clouds + 1); adj_ja = c_null_ptr queries nnz, n_pairs and edge_offsets
+     integer(c_int) function athena_mp_knn_graph_batched_host(n_clouds, n, offsets, dim, points, k, radius, mode, add_self_loops, &
+          adj_ia, adj_ja, capacity, nnz, coords, coords_capacity, n_pairs, edge_offsets) &
+          bind(C, name="athena_mp_knn_graph_batched_host")
+       import :: c_int, c_int32_t, c_int64_t, c_float, c_ptr
+       integer(c_int32_t), value :: n_clouds, n, dim, k, mode, add_self_loops
+       integer(c_int32_t), intent(in) :: offsets(*)
+       real(c_float), intent(in) :: points(dim, *)
+       real(c_float), value :: radius
+       type(c_ptr), value :: adj_ia, adj_ja, coords, edge_offsets
+       integer(c_int64_t), value :: capacity, coords_capacity
+       integer(c_int64_t), intent(out) :: nnz, n_pairs
+     end function
+     !! the search of the last k-nearest-neighbour call: queries, candidates examined, cells visited, the largest shell
+     integer(c_int) function athena_mp_knn_stats(out) bind(C, name="athena_mp_knn_stats")
+       import :: c_int, c_int64_t
+       integer(c_int64_t), intent(out) :: out(4)
      end function
      !! periodic structures -> pair list and edge geometry on the device, a batch per call (replaces get_graph_from_basis;
      !! definition: include/athena_mp.h).  offsets (n_structures + 1) and pbc (3) on the host; frac (3, n_atoms) and

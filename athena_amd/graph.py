@@ -18,6 +18,17 @@ import numpy as np
 from . import _capi
 
 
+def _knn_radius(radius):
+    """the cap of the k-nearest-neighbour builders: None = +infinity = no cap"""
+    return float("inf") if radius is None else float(radius)
+
+
+def _knn_mode(mode):
+    if mode not in ("union", "mutual", 0, 1):
+        raise ValueError('mode must be "union" or "mutual"')
+    return {"union": 0, "mutual": 1}.get(mode, mode)
+
+
 def _structure_arrays(frac, lat, offsets, pbc):
     """the inputs of the periodic builders as the C ABI takes them: frac [n, 3] / lat [B, 3, 3] float32, offsets [B + 1] and
     pbc [3] int32 on the host"""
@@ -251,6 +262,45 @@ class graph_type:
         self.num_edges = int(E.value)
         self.adj_ia, self.adj_ja = ia, ja
         return coords, eoff
+
+    def generate_knn_batch_adjacency_device(self, points, offsets, k, radius=None, mode="union", add_self_loops=False):
+        """The k-nearest-neighbour graphs of a batch of point clouds as ONE block-diagonal graph, built on the GPU
+        (athena_mp_knn_graph_batched_host; the definition is in include/athena_mp.h): every point is joined to the first k others
+        of its cloud in the order (fp32 squared distance, index), inside radius when one is given; mode "union" keeps a pair
+        either end chose, "mutual" one both chose.  Sets num_vertices (when unset), num_edges, adj_ia, adj_ja and returns
+        (coords [num_edges, dim] = p_i - p_j, edge_offsets [B + 1] int64) as numpy.  The host-array sibling of
+        DeviceGraph.from_point_clouds_knn."""
+        pts = np.ascontiguousarray(points, dtype=np.float32)
+        off = np.ascontiguousarray(offsets, dtype=np.int32)
+        if pts.ndim != 2 or off.ndim != 1 or off.size < 1:
+            raise ValueError("points must be [n, dim] and offsets [B + 1]")
+        n, dim = pts.shape
+        B = off.size - 1
+        if self.num_vertices == 0:
+            self.num_vertices = n
+        if n != self.num_vertices:
+            raise ValueError("points must hold one row per vertex")
+        _capi.init(0)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        nnz, E = C.c_int64(), C.c_int64()
+        head = (B, n, vp(off), dim, vp(pts), int(k), _knn_radius(radius), _knn_mode(mode), int(bool(add_self_loops)))
+        _capi.call("athena_mp_knn_graph_batched_host", *head, None, None, 0, C.byref(nnz), None, 0, C.byref(E), None)
+        ia = np.empty(n + 1, np.int32)
+        ja = np.empty((2, nnz.value), np.int32, order="F")
+        coords = np.empty((E.value, dim), np.float32)
+        eoff = np.empty(B + 1, np.int64)
+        _capi.call("athena_mp_knn_graph_batched_host", *head, vp(ia), vp(ja), nnz.value, C.byref(nnz), vp(coords), E.value,
+                   C.byref(E), vp(eoff))
+        self.num_edges = int(E.value)
+        self.adj_ia, self.adj_ja = ia, ja
+        return coords, eoff
+
+    def generate_knn_adjacency_device(self, points, k, radius=None, mode="union", add_self_loops=False):
+        """generate_knn_batch_adjacency_device for one cloud; returns coords [num_edges, dim]."""
+        pts = np.ascontiguousarray(points, dtype=np.float32)
+        if pts.ndim != 2:
+            raise ValueError("points must be [n, dim]")
+        return self.generate_knn_batch_adjacency_device(pts, [0, pts.shape[0]], k, radius, mode, add_self_loops)[0]
 
     def generate_periodic_adjacency_device(self, frac, lat, offsets, cutoff_min, cutoff_max, pbc=(1, 1, 1), add_self_loops=False):
         """The neighbour graphs of a batch of periodic structures as ONE block-diagonal graph, built on the GPU
@@ -521,6 +571,68 @@ class DeviceGraph:
         if want_adjacency:
             return self, coords, off.copy(), eoff, ia, np.asfortranarray(ja[:, :self.nnz])
         return self, coords, off.copy(), eoff
+
+    @classmethod
+    def from_point_clouds_knn(cls, points, offsets, k, radius=None, mode="union", add_self_loops=False, want_adjacency=False,
+                              want_neighbours=False, device=0):
+        """A batch of point clouds -> one block-diagonal k-nearest-neighbour device handle without the pair list leaving HBM
+        (athena_mp_knn_pairs_batched, then athena_mp_graph_create_from_edges_dev).  Every point is joined to the first k others
+        of its cloud in the order (fp32 squared distance, index) -- inside radius when one is given --; mode "union" keeps a pair
+        either end chose, "mutual" one both chose (the definition is in include/athena_mp.h).  points and offsets as in
+        from_point_clouds.  One search into buffers of n * k pairs, narrowed afterwards.  Returns what from_point_clouds returns
+        -- (handle, coords, vertex_offsets, edge_offsets) or, with want_adjacency, (..., adj_ia, adj_ja) -- and, with
+        want_neighbours, nbr last: a device tensor [n, k] int32, row i = the chosen neighbours of i as 1-based global ids in key
+        order, padded with 0."""
+        import torch
+
+        _capi.init(device)
+        dev = torch.device("cuda", device)
+        if isinstance(points, torch.Tensor):
+            pts = points.to(dev, torch.float32).contiguous()
+        else:
+            pts = torch.from_numpy(np.ascontiguousarray(points, dtype=np.float32)).to(dev)
+        off = np.ascontiguousarray(offsets, dtype=np.int32)
+        if pts.dim() != 2 or off.ndim != 1 or off.size < 1:
+            raise ValueError("points must be [n, dim] and offsets [B + 1]")
+        n, dim, B, k = int(pts.shape[0]), int(pts.shape[1]), int(off.size - 1), int(k)
+        _capi.use_torch_stream()
+        ptr = lambda t: C.c_void_p(t.data_ptr())
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        E = C.c_int64()
+        eoff = np.empty(B + 1, np.int64)
+        cap = n * max(min(k, 64), 1)             # a k outside 1..64 is the library's to refuse
+        pairs = torch.empty((cap, 2), dtype=torch.int32, device=dev)           # the memory of a column-major [2, cap]
+        coords = torch.empty((cap, dim), dtype=torch.float32, device=dev)
+        nbr = torch.empty((n, max(min(k, 64), 1)), dtype=torch.int32, device=dev) if want_neighbours else None
+        _capi.call("athena_mp_knn_pairs_batched", B, n, vp(off), dim, ptr(pts), k, _knn_radius(radius), _knn_mode(mode),
+                   ptr(nbr) if nbr is not None else None, ptr(pairs), ptr(coords), cap, vp(eoff), C.byref(E))
+        pairs, coords = pairs[:E.value].clone(), coords[:E.value].clone()      # narrowed: the n * k buffers go back
+        self = cls.__new__(cls)
+        ia = np.empty(n + 1, np.int32)
+        nnz = C.c_int64()
+        h = C.c_void_p()
+        ja = np.empty((2, 2 * E.value + n), np.int32, order="F") if want_adjacency else None
+        _capi.call("athena_mp_graph_create_from_edges_dev", n, E.value, ptr(pairs), int(bool(add_self_loops)), 1, vp(ia),
+                   vp(ja) if ja is not None else None, ja.shape[1] if ja is not None else 0, C.byref(nnz), C.byref(h))
+        self.handle = h
+        self.n_rows = self.n_cols = n
+        self.nnz = int(nnz.value)
+        self.n_edge_cols = int(E.value)
+        out = (self, coords, off.copy(), eoff)
+        if want_adjacency:
+            out += (ia, np.asfortranarray(ja[:, :self.nnz]))
+        if want_neighbours:
+            out += (nbr,)
+        return out
+
+    @classmethod
+    def from_points_knn(cls, points, k, radius=None, mode="union", add_self_loops=False, want_adjacency=False,
+                        want_neighbours=False, device=0):
+        """from_point_clouds_knn for one cloud.  Returns what from_points returns -- (handle, coords) or (handle, coords, adj_ia,
+        adj_ja) -- with nbr added last when want_neighbours."""
+        n = int(points.shape[0])
+        out = cls.from_point_clouds_knn(points, [0, n], k, radius, mode, add_self_loops, want_adjacency, want_neighbours, device)
+        return out[:2] + out[4:]
 
     @classmethod
     def from_structures(cls, frac, lat, offsets, cutoff_min, cutoff_max, pbc=(1, 1, 1), add_self_loops=False, want_adjacency=False,

@@ -168,6 +168,46 @@ int athena_mp_radius_graph_batched_host(int32_t n_clouds, int32_t n, const int32
                                         const float *points_host, float radius, int32_t add_self_loops, int32_t *adj_ia_out,
                                         int32_t *adj_ja_out, int64_t capacity, int64_t *nnz_out, float *coords_out,
                                         int64_t coords_capacity, int64_t *n_pairs_out, int64_t *edge_offsets_out);
+/* A batch of point clouds -> ONE block-diagonal k-nearest-neighbour graph on the device (knn_graph.hip): the neighbour cap beside
+ * the radius graphs above, for clouds whose density varies by orders of magnitude.  Every implementation gives the same arrays.
+ *   points [n, dim] fp32 row-major on the device, dim in 1..3; offsets [n_clouds + 1] int32 on the HOST, 0-based, as in
+ *   athena_mp_radius_pairs_batched.  The candidates of point i are the other points j != i of its own cloud.
+ *   Distance: s(i, j) is the squared distance of athena_mp_radius_pairs, unchanged: d = p_i - p_j per component,
+ *   s = ((d0*d0) + d1*d1) + d2*d2, every operation rounded to fp32 on its own.  It is symmetric in i and j bit for bit.
+ *   Order: the candidates of i are ordered by the key (s(i, j), j): s first, then the smaller index (on a lattice the tie rule
+ *   decides the graph, so it is part of the definition).  N_k(i) is the first min(k, candidates) candidates in that order.
+ *   Radius cap: with a finite radius only candidates with s <= fl(radius * radius) count (the radius builder's predicate);
+ *   radius = +infinity means no cap.  1 <= k <= 64.
+ *   Directed output: nbr [n, k] int32 (may be NULL): row i holds N_k(i) as 1-based global ids in key order, padded with 0.
+ *   Undirected output: a pair i < j is an edge in mode 0 (union) iff j in N_k(i) or i in N_k(j), in mode 1 (mutual) iff both.
+ *   Pairs are numbered in lexicographic order of the global (i, j): pairs [2, capacity] column-major, 1-based; coords [capacity,
+ *   dim], coords[e, :] = p_i - p_j; edge_offsets [n_clouds + 1] int64 on the HOST (may be NULL), edge_offsets[b] = the number of
+ *   pairs whose i is below offsets[b] -- the conventions of athena_mp_radius_pairs_batched, so athena_mp_graph_create_from_edges_dev,
+ *   athena_mp_batch_plan_create and athena_mp_edge_grad_to_points take the result as it is.
+ * nbr_dev, pairs_dev and coords_dev all NULL: size query (edge_offsets is still filled).  capacity = n * k always suffices, so a
+ * caller can run the search once and narrow afterwards.  Refused with a message: dim outside 1..3; k outside 1..64; a radius that
+ * is NaN or <= 0; a mode other than 0 or 1; n_clouds < 0, offsets[0] != 0, a descending offset, offsets[n_clouds] != n (the
+ * wording of athena_mp_radius_pairs_batched); a non-finite coordinate (cloud, component and point of the first one are named,
+ * 1-based); n * k >= 2^31; capacity < pairs.  The library stays usable after a refusal.  Two builds of the same input are
+ * byte-identical.  Worst case: with no cap and clusters far apart that hold fewer than k + 1 points each, a query visits every
+ * cell of its cloud's grid -- correct and slow; the cap is the remedy. */
+int athena_mp_knn_pairs_batched(int32_t n_clouds, int32_t n, const int32_t *offsets_host, int32_t dim, const float *points_dev,
+                                int32_t k, float radius, int32_t mode, int32_t *nbr_dev, int32_t *pairs_dev, float *coords_dev,
+                                int64_t capacity, int64_t *edge_offsets_host, int64_t *n_pairs_out);
+/* The same for one cloud of n points. */
+int athena_mp_knn_pairs(int32_t n, int32_t dim, const float *points_dev, int32_t k, float radius, int32_t mode, int32_t *nbr_dev,
+                        int32_t *pairs_dev, float *coords_dev, int64_t capacity, int64_t *n_pairs_out);
+/* The same with every array on the host, for callers that hold Fortran arrays: clouds -> adj_ia [n+1], adj_ja [2, capacity]
+ * column-major (what generate_adjacency [+ add_self_loops] makes of the pair list), coords [coords_capacity, dim] and
+ * edge_offsets [n_clouds + 1] (may be NULL).  adj_ja_out == NULL: size query for both counts (*nnz_out, *n_pairs_out) and
+ * edge_offsets. */
+int athena_mp_knn_graph_batched_host(int32_t n_clouds, int32_t n, const int32_t *offsets_host, int32_t dim, const float *points_host,
+                                     int32_t k, float radius, int32_t mode, int32_t add_self_loops, int32_t *adj_ia_out,
+                                     int32_t *adj_ja_out, int64_t capacity, int64_t *nnz_out, float *coords_out,
+                                     int64_t coords_capacity, int64_t *n_pairs_out, int64_t *edge_offsets_out);
+/* What the search of the last k-nearest-neighbour call did: out[0] = query points, out[1] = candidates examined (distances
+ * evaluated), out[2] = grid cells visited, out[3] = the largest shell (Chebyshev cell distance) any query reached. */
+int athena_mp_knn_stats(int64_t out[4]);
 /* Periodic structures -> neighbour graphs on the device, a batch per call (periodic_graph.hip).  It replaces get_graph_from_basis
  * of the reference's chemical examples (example/example_library/src/mod_read_chemical_graphs.f90:196-278); the step in front of
  * athena_mp_graph_create_from_edges_dev.
