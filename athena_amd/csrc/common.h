@@ -166,6 +166,34 @@ int graph_build_device(athena_mp_graph *g, const int32_t *adj_ja, const std::vec
 int csr_from_edges_core(int32_t n_vertices, int64_t n_pairs, const int32_t *index_list, int32_t add_self_loops,
                         int32_t *adj_ia_out, int32_t *adj_ja_out, int64_t capacity, int64_t *nnz_out,
                         int32_t **keep_ja_dev, bool list_on_device = false);
+// The end of a point-cloud *_graph_host entry (radius_graph.hip, knn_graph.hip) once the pair count E is known: the sizes out,
+// the size query's return, the capacity checks, then pairs(&d_pairs, &d_coords) -- the E pairs [2, E] and coords [E, dim] on the
+// device, built or already there -- the coords home and the CSR through csr_from_edges_core.
+template <typename Pairs>
+int graph_host_tail(const char *who, int32_t n, int32_t dim, int64_t E, int32_t add_self_loops, int32_t *adj_ia_out, int32_t *adj_ja_out,
+                    int64_t capacity, int64_t *nnz_out, float *coords_out, int64_t coords_capacity, int64_t *n_pairs_out, hipStream_t st,
+                    Pairs pairs)
+{
+    // no self pair and no duplicate pair: every pair is two entries, every vertex gets its loop when asked
+    const int64_t nnz = 2 * E + (add_self_loops ? n : 0);
+    *n_pairs_out = E;
+    *nnz_out = nnz;
+    if (adj_ja_out == nullptr) return 0;                          // size query
+    AMP_REQUIRE(adj_ia_out != nullptr && (coords_out != nullptr || E == 0), "%s: null output array", who);
+    AMP_REQUIRE(capacity >= nnz, "%s: adj_ja buffer holds %lld entries, the graph has %lld", who, (long long)capacity, (long long)nnz);
+    AMP_REQUIRE(coords_capacity >= E, "%s: coords buffer holds %lld pairs, the graph has %lld", who, (long long)coords_capacity,
+                (long long)E);
+    int32_t *d_pairs = nullptr;
+    float *d_coords = nullptr;
+    if (int rc = pairs(&d_pairs, &d_coords)) return rc;
+    if (E > 0) AMP_HIP(hipMemcpyAsync(coords_out, d_coords, sizeof(float) * (size_t)E * dim, hipMemcpyDeviceToHost, st));
+    int64_t nnz_built = 0;
+    if (int rc = amp::csr_from_edges_core(n, E, d_pairs, add_self_loops, adj_ia_out, adj_ja_out, capacity, &nnz_built, nullptr, true))
+        return rc;
+    AMP_HIP(hipStreamSynchronize(st));
+    *nnz_out = nnz_built;
+    return 0;
+}
 // argument checks of the geometry gradients (geometry_grad.hip), shared with their *_host entries: 0, or 2 with the message set
 int points_grad_check(const athena_mp_graph *g, int32_t dim);
 int periodic_grad_check(const athena_mp_graph *g, int32_t B, int32_t n, const int32_t *offsets, const int64_t *edge_offsets,

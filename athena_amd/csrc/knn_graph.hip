@@ -12,7 +12,7 @@
 // so its bit pattern orders as an unsigned integer; it sits above j.
 //
 // How.  GRID: per cloud a bounding box and a uniform grid, cell keys in disjoint ranges per cloud, one stable radix sort of
-// (cell, point), positions in cell order -- the passes of radius_pairs_batched_core (cell_grid.h).  The cell width is free here:
+// (cell, point), positions in cell order -- build_cell_grid of cell_grid.h, as in radius_graph.hip.  The cell width is free here:
 // about kGridPoints points per cell, at most 2 m cells per cloud and kMaxCellsAxis per axis; an axis of zero extent is one cell.
 // SEARCH: one 64-lane wave per query point, in cell order.  The wave holds its best keys ascending across its lanes (one key per
 // lane; the first k count) and walks the cells around the point's own in shells of growing Chebyshev distance rho, 64 candidates
@@ -410,61 +410,28 @@ int knn_pairs_batched_core(int32_t B, int32_t n, const int32_t *offsets, int32_t
     const bool fill = pairs_dev != nullptr || coords_dev != nullptr;
 
     Scratch tmp;
-    BatchItems it;
-    std::vector<Box> box;
-    if (int rc = batch_boxes(who, B, offsets, dim, points_dev, st, tmp, it, box)) return rc;
-
-    // a grid per non-empty cloud; cell_base = the exclusive sum of the clouds' cell counts (an empty cloud adds 0)
-    std::vector<Grid> grids((size_t)B);
-    std::vector<WLow> wlow((size_t)B);
-    std::vector<uint32_t> cell_base((size_t)B + 1);
-    int64_t total_cells = 0;
-    for (int32_t b = 0; b < B; ++b) {
-        cell_base[b] = (uint32_t)total_cells;
-        const int32_t m = offsets[b + 1] - offsets[b];
-        grids[b] = Grid{};
-        wlow[b] = WLow{};
-        if (m == 0) continue;
-        grids[b] = make_knn_grid(box[b], dim, m, &wlow[b]);
-        total_cells += (int64_t)grids[b].nc[0] * grids[b].nc[1] * grids[b].nc[2];
-        AMP_REQUIRE(total_cells < (int64_t)INT32_MAX, "knn_pairs_batched: more than 2^31 grid cells over %d points", n);
-    }
-    cell_base[B] = (uint32_t)total_cells;
-    const uint32_t n_cells = (uint32_t)total_cells;
+    CellGrid cg;
+    std::vector<WLow> wlow((size_t)B);           // an empty cloud keeps zeros
+    if (int rc = build_cell_grid(who, true, B, n, offsets, dim, points_dev, st, tmp,
+                                 [&](const Box &box, int32_t m, int32_t b) { return make_knn_grid(box, dim, m, &wlow[b]); }, cg))
+        return rc;
+    const BatchItems &it = cg.it;
     const int64_t T = (int64_t)n * k;
 
-    Grid *d_grids = nullptr;
     WLow *d_wlow = nullptr;
-    uint32_t *d_cell_base = nullptr, *d_key = nullptr, *d_key_s = nullptr, *d_key_t = nullptr, *d_stat = nullptr;
-    int32_t *d_perm = nullptr, *d_perm_t = nullptr, *d_cell_start = nullptr, *d_nbr = nullptr;
-    float *d_sorted = nullptr;
+    uint32_t *d_stat = nullptr;
+    int32_t *d_nbr = nullptr;
     unsigned long long *d_stat_part = nullptr;
-    void *d_temp = nullptr;
-    if (tmp.get(&d_grids, B) || tmp.get(&d_wlow, B) || tmp.get(&d_cell_base, (size_t)B + 1) || tmp.get(&d_key, n) ||
-        tmp.get(&d_key_s, n) || tmp.get(&d_key_t, n) || tmp.get(&d_perm, n) || tmp.get(&d_perm_t, n) ||
-        tmp.get(&d_cell_start, (size_t)n_cells + 1) || tmp.get(&d_sorted, (size_t)n * dim) || tmp.get(&d_stat, 3 * (size_t)n) ||
-        tmp.get(&d_stat_part, 3 * (size_t)kStatBlocks) || tmp.get((char **)&d_temp, radix::scratch_bytes(n)))
-        return 1;
+    if (tmp.get(&d_wlow, B) || tmp.get(&d_stat, 3 * (size_t)n) || tmp.get(&d_stat_part, 3 * (size_t)kStatBlocks)) return 1;
     if (nbr_dev == nullptr) {
         if (tmp.get(&d_nbr, (size_t)T)) return 1;
     } else {
         d_nbr = nbr_dev;
     }
-    AMP_HIP(hipMemcpyAsync(d_grids, grids.data(), sizeof(Grid) * (size_t)B, hipMemcpyHostToDevice, st));
     AMP_HIP(hipMemcpyAsync(d_wlow, wlow.data(), sizeof(WLow) * (size_t)B, hipMemcpyHostToDevice, st));
-    AMP_HIP(hipMemcpyAsync(d_cell_base, cell_base.data(), sizeof(uint32_t) * ((size_t)B + 1), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(rgb_cell_key_kernel, dim3(it.item_blocks), dim3(64 * kItemWaves), 0, st, it.W, (const int32_t *)it.d_items, (int)dim,
-                       points_dev, (const Grid *)d_grids, (const uint32_t *)d_cell_base, d_key);
-    AMP_LAUNCH_CHECK();
-    if (int rc = radix::sort_pairs<uint32_t>((const uint32_t *)d_key, nullptr, n, bits_for(n_cells - 1), d_key_s, d_perm, d_key_t, d_perm_t,
-                                             d_temp, st))
-        return rc;
-    hipLaunchKernelGGL(rg_gather_points_kernel, dim3(blocks(n)), dim3(256), 0, st, n, (int)dim, points_dev, (const int32_t *)d_perm,
-                       d_sorted);
-    hipLaunchKernelGGL(rg_cell_start_kernel, dim3(blocks((int64_t)n_cells + 1)), dim3(256), 0, st, n_cells, (const uint32_t *)d_key_s, n,
-                       d_cell_start);
-    launch_search(dim, n, st, B, (const int32_t *)it.d_off, (const Grid *)d_grids, (const WLow *)d_wlow, (const uint32_t *)d_cell_base,
-                  (int)k, r2, (const float *)d_sorted, (const int32_t *)d_perm, (const int32_t *)d_cell_start, d_nbr, d_stat);
+    launch_search(dim, n, st, B, (const int32_t *)it.d_off, (const Grid *)cg.d_grids, (const WLow *)d_wlow,
+                  (const uint32_t *)cg.d_cell_base, (int)k, r2, (const float *)cg.d_sorted, (const int32_t *)cg.d_perm,
+                  (const int32_t *)cg.d_cell_start, d_nbr, d_stat);
     const int stat_blocks = (int)std::min<int64_t>(kStatBlocks, blocks(n));
     hipLaunchKernelGGL(knn_stat_kernel, dim3(stat_blocks), dim3(256), 0, st, n, (const uint32_t *)d_stat, d_stat_part);
     AMP_LAUNCH_CHECK();
@@ -475,9 +442,8 @@ int knn_pairs_batched_core(int32_t B, int32_t n, const int32_t *offsets, int32_t
     uint8_t *d_flag = nullptr;
     long long *d_edge_off = nullptr;
     void *d_temp2 = nullptr;
-    const uint32_t tiles = scan64::tiles(T);
     if (tmp.get(&d_pk, T) || tmp.get(&d_pk_s, T) || tmp.get(&d_pk_t, T) || tmp.get(&d_v, T) || tmp.get(&d_v_t, T) || tmp.get(&d_flag, T) ||
-        tmp.get(&d_tile, (size_t)tiles + 1) || tmp.get(&d_offset, T) || tmp.get(&d_edge_off, (size_t)B + 1) ||
+        tmp.get(&d_tile, (size_t)scan64::tiles(T) + 1) || tmp.get(&d_offset, T) || tmp.get(&d_edge_off, (size_t)B + 1) ||
         tmp.get((char **)&d_temp2, radix::scratch_bytes(T)))
         return 1;
     const unsigned long long pad = (unsigned long long)n * (unsigned long long)n;
@@ -487,16 +453,12 @@ int knn_pairs_batched_core(int32_t B, int32_t n, const int32_t *offsets, int32_t
                                                        d_temp2, st))
         return rc;
     hipLaunchKernelGGL(knn_flag_kernel, dim3(blocks(T)), dim3(256), 0, st, T, pad, (int)mode, (const unsigned long long *)d_pk_s, d_flag);
-    hipLaunchKernelGGL(scan64::tile_sum_kernel<uint8_t>, dim3(tiles), dim3(256), 0, st, T, (const uint8_t *)d_flag, d_tile);
-    hipLaunchKernelGGL(scan64::scan_tiles_kernel, dim3(1), dim3(256), 0, st, tiles, d_tile);
-    hipLaunchKernelGGL(scan64::apply_kernel<uint8_t>, dim3(tiles), dim3(256), 0, st, T, (const uint8_t *)d_flag,
-                       (const unsigned long long *)d_tile, d_offset);
+    const unsigned long long *d_total = scan64::exclusive(T, (const uint8_t *)d_flag, d_tile, d_offset, st);
     hipLaunchKernelGGL(knn_edge_offsets_kernel, dim3(blocks((int64_t)B + 1)), dim3(256), 0, st, B, n, T, (const int32_t *)it.d_off,
-                       (const unsigned long long *)d_pk_s, (const unsigned long long *)d_offset,
-                       (const unsigned long long *)(d_tile + tiles), d_edge_off);
+                       (const unsigned long long *)d_pk_s, (const unsigned long long *)d_offset, d_total, d_edge_off);
     AMP_LAUNCH_CHECK();
     unsigned long long total = 0, stat_part[3 * kStatBlocks];
-    AMP_HIP(hipMemcpyAsync(&total, d_tile + tiles, sizeof(total), hipMemcpyDeviceToHost, st));
+    AMP_HIP(hipMemcpyAsync(&total, d_total, sizeof(total), hipMemcpyDeviceToHost, st));
     AMP_HIP(hipMemcpyAsync(stat_part, d_stat_part, sizeof(unsigned long long) * 3 * (size_t)stat_blocks, hipMemcpyDeviceToHost, st));
     if (edge_offsets_out)
         AMP_HIP(hipMemcpyAsync(edge_offsets_out, d_edge_off, sizeof(int64_t) * ((size_t)B + 1), hipMemcpyDeviceToHost, st));
@@ -569,21 +531,10 @@ extern "C" int athena_mp_knn_graph_batched_host(int32_t n_clouds, int32_t n, con
     if (int rc = amp::knn_pairs_batched_core(n_clouds, n, offsets_host, dim, d_pts, k, radius, mode, nullptr, d_pairs, d_coords, T,
                                              edge_offsets_out, &E))
         return rc;
-    // no self pair and no duplicate pair: every pair is two entries, every vertex gets its loop when asked
-    const int64_t nnz = 2 * E + (add_self_loops ? n : 0);
-    *n_pairs_out = E;
-    *nnz_out = nnz;
-    if (adj_ja_out == nullptr) return 0;                          // size query
-    AMP_REQUIRE(adj_ia_out != nullptr && (coords_out != nullptr || E == 0), "knn_graph_batched_host: null output array");
-    AMP_REQUIRE(capacity >= nnz, "knn_graph_batched_host: adj_ja buffer holds %lld entries, the graph has %lld", (long long)capacity,
-                (long long)nnz);
-    AMP_REQUIRE(coords_capacity >= E, "knn_graph_batched_host: coords buffer holds %lld pairs, the graph has %lld",
-                (long long)coords_capacity, (long long)E);
-    if (E > 0) AMP_HIP(hipMemcpyAsync(coords_out, d_coords, sizeof(float) * (size_t)E * dim, hipMemcpyDeviceToHost, st));
-    int64_t nnz_built = 0;
-    if (int rc = amp::csr_from_edges_core(n, E, d_pairs, add_self_loops, adj_ia_out, adj_ja_out, capacity, &nnz_built, nullptr, true))
-        return rc;
-    AMP_HIP(hipStreamSynchronize(st));
-    *nnz_out = nnz_built;
-    return 0;
+    return amp::graph_host_tail("knn_graph_batched_host", n, dim, E, add_self_loops, adj_ia_out, adj_ja_out, capacity, nnz_out, coords_out,
+                           coords_capacity, n_pairs_out, st, [&](int32_t **pairs, float **coords) {      // already there
+                               *pairs = d_pairs;
+                               *coords = d_coords;
+                               return 0;
+                           });
 }

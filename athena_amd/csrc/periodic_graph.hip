@@ -90,6 +90,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "cell_start.h"
 #include "common.h"
 #include "radix_sort.h"
 #include "scan64.h"
@@ -428,20 +429,6 @@ __global__ __launch_bounds__(256) void pg_cell_key_kernel(int32_t NG, const PgGr
     key[ga] = (uint32_t)S.c0 + c;
 }
 
-// cell_start[c] = first slot whose sorted key is >= c  (c = 0 .. n_cells)
-__global__ __launch_bounds__(256) void pg_cell_start_kernel(uint32_t n_cells, const uint32_t *__restrict__ sorted_key, int32_t NG,
-                                                            int32_t *__restrict__ cell_start)
-{
-    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (c > (int64_t)n_cells) return;
-    int32_t lo = 0, hi = NG;
-    while (lo < hi) {
-        const int32_t mid = lo + ((hi - lo) >> 1);
-        if ((int64_t)sorted_key[mid] < c) lo = mid + 1; else hi = mid;
-    }
-    cell_start[c] = lo;
-}
-
 // One thread per grid atom i: its partners j >= i in the cells -1, 0, +1 (circular) of every axis with more than one cell.  perm
 // lists the grid atoms in cell order, ascending inside a cell.  FILL = false: count[i] (and count[NG] = 0, the scan's end).
 // FILL = true: key[poff[i] + t] = i * NG + j for the t-th partner met.
@@ -519,14 +506,6 @@ __global__ __launch_bounds__(64 * kWaves) void pg_grid_walk_kernel(int32_t n_ite
     const unsigned long long end = pg_walk_item<FILL, true>(frac + 3 * (int64_t)v0, m, i0, i1, v0, lat + 9 * (int64_t)s, I, pbc, cutoff_min,
                                                             cutoff_max, base, out, cd);
     if (!FILL && lane == 0) item_count[w] = end;
-}
-
-inline unsigned pg_blocks(int64_t n) { return (unsigned)((n + 255) / 256); }
-inline int pg_bits_for(unsigned long long max_value)
-{
-    int b = 1;
-    while (b < 64 && (max_value >> b)) ++b;
-    return b;
 }
 
 } // namespace
@@ -660,27 +639,23 @@ int periodic_pairs_core(int32_t B, int32_t n, const int32_t *offsets, const floa
         int32_t *d_perm = nullptr, *d_perm_t = nullptr, *d_cell_start = nullptr;
         unsigned long long *d_ptile = nullptr;
         void *d_temp = nullptr;
-        const uint32_t ptiles = scan64::tiles(NG + 1);
         if (tmp.get(&d_gs, (size_t)G + 1) || tmp.get(&d_ck, NG) || tmp.get(&d_ck_s, NG) || tmp.get(&d_ck_t, NG) || tmp.get(&d_perm, NG) ||
             tmp.get(&d_perm_t, NG) || tmp.get(&d_cell_start, (size_t)NC + 1) || tmp.get(&d_cnt, (size_t)NG + 1) ||
-            tmp.get(&d_ptile, (size_t)ptiles + 1) || tmp.get(&d_poff, (size_t)NG + 1) || tmp.get((char **)&d_temp, radix::scratch_bytes(NG)))
+            tmp.get(&d_ptile, (size_t)scan64::tiles(NG + 1) + 1) || tmp.get(&d_poff, (size_t)NG + 1) || tmp.get((char **)&d_temp, radix::scratch_bytes(NG)))
             return 1;
         AMP_HIP(hipMemcpyAsync(d_gs, gs.data(), sizeof(PgGridS) * ((size_t)G + 1), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(pg_cell_key_kernel, dim3(pg_blocks(NG)), dim3(256), 0, st, (int32_t)NG, (const PgGridS *)d_gs, G,
+        hipLaunchKernelGGL(pg_cell_key_kernel, dim3(blocks(NG)), dim3(256), 0, st, (int32_t)NG, (const PgGridS *)d_gs, G,
                            (const int32_t *)d_off, frac_dev, d_ck);
         AMP_LAUNCH_CHECK();
-        if (int rc = radix::sort_pairs<uint32_t>((const uint32_t *)d_ck, nullptr, NG, pg_bits_for((unsigned long long)NC - 1ull), d_ck_s, d_perm,
+        if (int rc = radix::sort_pairs<uint32_t>((const uint32_t *)d_ck, nullptr, NG, bits_for((unsigned long long)NC - 1ull), d_ck_s, d_perm,
                                                  d_ck_t, d_perm_t, d_temp, st))
             return rc;
-        hipLaunchKernelGGL(pg_cell_start_kernel, dim3(pg_blocks(NC + 1)), dim3(256), 0, st, (uint32_t)NC, (const uint32_t *)d_ck_s, (int32_t)NG,
+        hipLaunchKernelGGL(rg_cell_start_kernel, dim3(blocks(NC + 1)), dim3(256), 0, st, (uint32_t)NC, (const uint32_t *)d_ck_s, (int32_t)NG,
                            d_cell_start);
-        hipLaunchKernelGGL(pg_partner_kernel<false>, dim3(pg_blocks(NG + 1)), dim3(256), 0, st, (int32_t)NG, (const PgGridS *)d_gs, G,
+        hipLaunchKernelGGL(pg_partner_kernel<false>, dim3(blocks(NG + 1)), dim3(256), 0, st, (int32_t)NG, (const PgGridS *)d_gs, G,
                            (const uint32_t *)d_ck, (const int32_t *)d_perm, (const int32_t *)d_cell_start, d_cnt,
                            (const unsigned long long *)nullptr, (unsigned long long *)nullptr);
-        hipLaunchKernelGGL(scan64::tile_sum_kernel<uint32_t>, dim3(ptiles), dim3(256), 0, st, NG + 1, (const uint32_t *)d_cnt, d_ptile);
-        hipLaunchKernelGGL(scan64::scan_tiles_kernel, dim3(1), dim3(256), 0, st, ptiles, d_ptile);
-        hipLaunchKernelGGL(scan64::apply_kernel<uint32_t>, dim3(ptiles), dim3(256), 0, st, NG + 1, (const uint32_t *)d_cnt,
-                           (const unsigned long long *)d_ptile, d_poff);
+        (void)scan64::exclusive(NG + 1, (const uint32_t *)d_cnt, d_ptile, d_poff, st);
         AMP_LAUNCH_CHECK();
         poff.resize((size_t)NG + 1);
         AMP_HIP(hipMemcpyAsync(poff.data(), d_poff, sizeof(unsigned long long) * poff.size(), hipMemcpyDeviceToHost, st));
@@ -701,13 +676,13 @@ int periodic_pairs_core(int32_t B, int32_t n, const int32_t *offsets, const floa
         if (tmp.get(&d_pk, NP) || tmp.get(&d_key, NP) || tmp.get(&d_pk_t, NP) || tmp.get(&d_v, NP) || tmp.get(&d_v_t, NP) ||
             tmp.get((char **)&d_temp2, radix::scratch_bytes(NP)))
             return 1;
-        hipLaunchKernelGGL(pg_partner_kernel<true>, dim3(pg_blocks(NG + 1)), dim3(256), 0, st, (int32_t)NG, (const PgGridS *)d_gs, G,
+        hipLaunchKernelGGL(pg_partner_kernel<true>, dim3(blocks(NG + 1)), dim3(256), 0, st, (int32_t)NG, (const PgGridS *)d_gs, G,
                            (const uint32_t *)d_ck, (const int32_t *)d_perm, (const int32_t *)d_cell_start, (uint32_t *)nullptr,
                            (const unsigned long long *)d_poff, d_pk);
         AMP_LAUNCH_CHECK();
         // rows are already in order of i; the sort of the whole key orders the partners inside every row
         if (int rc = radix::sort_pairs<unsigned long long>((const unsigned long long *)d_pk, nullptr, NP,
-                                                           pg_bits_for((unsigned long long)NG * (unsigned long long)NG - 1ull), d_key, d_v,
+                                                           bits_for((unsigned long long)NG * (unsigned long long)NG - 1ull), d_key, d_v,
                                                            d_pk_t, d_v_t, d_temp2, st))
             return rc;
         g_periodic_stats[3] = NP;

@@ -1,21 +1,30 @@
-// Points -> radius graph on the device: the step in front of athena_mp_csr_from_edges / athena_mp_graph_create_from_edges for
-// graph_nop_layer_type's inputs (a radius graph of a point cloud and its edge geometry, athena_graph_nop_layer.f90:743-758).
-// graphstruc has no such call.
+// Points -> radius graph on the device, one cloud or a batch of clouds as one block-diagonal pair list: the step in front of
+// athena_mp_csr_from_edges / athena_mp_graph_create_from_edges for graph_nop_layer_type's inputs (a radius graph of a point cloud
+// and its edge geometry, athena_graph_nop_layer.f90:743-758).  graphstruc has no such call.
 //
 // The definition (every implementation gives the same arrays; tests compare with np.array_equal):
 //   * delta = p_i - p_j component by component in fp32, s = ((d0*d0) + d1*d1) + d2*d2 with every multiply and add rounded to
-//     fp32 on its own (the library is built with -ffp-contract=off); i < j are joined iff s <= fl(radius * radius).  No self
-//     pairs; two points at the same place are joined.
-//   * pairs are numbered in lexicographic order of (i, j), i < j; coords[e, :] = p_i - p_j (smaller index minus larger).
+//     fp32 on its own (the library is built with -ffp-contract=off); i < j of ONE cloud are joined iff s <= fl(radius * radius).
+//     No self pairs; two points at the same place are joined.
+//   * pairs are numbered in lexicographic order of the global (i, j), i < j; coords[e, :] = p_i - p_j (smaller index minus
+//     larger); edge_offsets[b] = pairs whose i is below offsets[b] (include/athena_mp.h).
+// So a batch gives the pair lists of its slices points[offsets[b] : offsets[b+1]], in cloud order, offsets[b] added to both indices.
 //
-// How: a uniform grid (its passes are in cell_grid.h, shared with knn_graph.hip) whose cells are at least radius * (1 + 2^-10)
-// wide on every axis, at most kMaxCellsAxis cells per axis and
-// at most 2 n cells in all; a stable radix sort of (cell, point id) (radix_sort.h), the positions copied into cell order; a COUNT
-// pass in which every point counts its partners with a larger id in the 3^dim cells around it; an exclusive scan of the counts
-// IN POINT-ID ORDER (64-bit offsets, scan64.h), so the rows of the pair list already sit in lexicographic order of i; a FILL pass that
-// writes the keys i * n + j into those rows; one radix sort of the keys, which puts the partners of every row in ascending
-// order; one pass that decodes the keys into the 1-based pair list and the coordinate differences.  No atomics on data: counts,
-// offsets and the final order are functions of the input alone.
+// How, in ONE pipeline (radius_pairs_batched_core; the single-cloud entries run it with offsets = {0, n}).  The grid set-up is
+// build_cell_grid of cell_grid.h, shared with knn_graph.hip: the host cuts the clouds into work items (cloud, points p0 .. p1-1)
+// of at most kItemPoints points, one 64-lane wave each; a bounding box per item (min and max are order-free; a wave folds with
+// __shfl_xor and writes its own slot), folded per cloud in item order; the boxes come home and make_grid runs per cloud -- cells
+// at least radius * (1 + 2^-10) wide on every axis, at most kMaxCellsAxis cells per axis, at most 2 m_b per cloud and so at most
+// 2 n in all; a cloud's cells are the keys [cell_base[b], cell_base[b+1]): disjoint ranges, so after the key pass no kernel sees
+// a candidate pair of two clouds; a stable radix sort of (cell, point id) (radix_sort.h), the positions copied into cell order,
+// the cell starts.  Then a COUNT pass in which every point counts its partners with a larger id in the 3^dim cells around it -- a
+// thread looks up its cloud (the last b with offsets[b] <= i: empty clouds repeat a value and own no point) and loads that
+// cloud's grid; an exclusive scan of the counts IN POINT-ID ORDER (64-bit offsets, scan64.h), so the rows of the pair list already
+// sit in lexicographic order of i; a FILL pass that writes keys into those rows; one radix sort of the keys, which puts the
+// partners of every row in ascending order; one pass that decodes the keys into the 1-based pair list and the coordinate
+// differences.  Both ends of a pair are in one cloud, so the key is i * M + (j - offsets[b]) with M the largest cloud: the order
+// is that of (i, j), in fewer bits than i * n + j (one cloud: M = n, the key is i * n + j).  No atomics on data: counts, offsets
+// and the final order are functions of the input alone; every access to points and coords is 4 bytes wide.
 //
 // Why the margin: the cell of a coordinate is floor(fl(fl(p - lo) * inv_w)) clamped to the axis -- monotone in p, each of the two
 // roundings within 2^-24 relative, so a computed cell coordinate q is within 3 * 2^-24 * q <= 3 * 2^-24 * kMaxCellsAxis of the
@@ -34,7 +43,6 @@
 namespace {
 
 constexpr double kCellMargin = 1.0 / 1024.0;
-constexpr int kBoxBlocks = 512;
 
 // ---- the predicate, term by term in fp32 (-ffp-contract=off: no fused multiply-add) --------------------------------------------
 template <int DIM> __device__ inline bool joined(const float *__restrict__ a, const float *__restrict__ b, float r2)
@@ -52,266 +60,8 @@ template <int DIM> __device__ inline bool joined(const float *__restrict__ a, co
     return s <= r2;
 }
 
-// One thread per slot of the cell order: the point i = perm[slot] against every point j > i of the 3^DIM cells around its own.
-// FILL = false: count[i] = number of partners.  FILL = true: key[offset[i] + t] = i * n + j for the t-th partner found.
-template <int DIM, bool FILL>
-__global__ __launch_bounds__(256) void rg_neighbour_kernel(int32_t n, Grid g, float r2, const float *__restrict__ sorted,
-                                                           const int32_t *__restrict__ perm, const uint32_t *__restrict__ sorted_key,
-                                                           const int32_t *__restrict__ cell_start, uint32_t *__restrict__ count,
-                                                           const unsigned long long *__restrict__ offset,
-                                                           unsigned long long *__restrict__ key)
-{
-    const int64_t slot = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (slot >= n) return;
-    const int32_t i = perm[slot];
-    float p[3] = {0.f, 0.f, 0.f};
-#pragma unroll
-    for (int a = 0; a < DIM; ++a) p[a] = sorted[slot * DIM + a];
-    uint32_t c = sorted_key[slot];
-    int32_t cc[3] = {0, 0, 0};
-#pragma unroll
-    for (int a = 0; a < DIM; ++a) {
-        cc[a] = (int32_t)(c % (uint32_t)g.nc[a]);
-        c /= (uint32_t)g.nc[a];
-    }
-    uint32_t found = 0;
-    unsigned long long at = 0;
-    if (FILL) at = offset[i];
-    const int z0 = DIM > 2 ? max(cc[2] - 1, 0) : 0, z1 = DIM > 2 ? min(cc[2] + 1, g.nc[2] - 1) : 0;
-    const int y0 = DIM > 1 ? max(cc[1] - 1, 0) : 0, y1 = DIM > 1 ? min(cc[1] + 1, g.nc[1] - 1) : 0;
-    const int x0 = max(cc[0] - 1, 0), x1 = min(cc[0] + 1, g.nc[0] - 1);
-    for (int z = z0; z <= z1; ++z)
-        for (int y = y0; y <= y1; ++y) {
-            // the cells x0 .. x1 of one grid row are consecutive keys: one contiguous run of slots
-            const uint32_t row = (DIM > 2 ? (uint32_t)z * (uint32_t)g.nc[1] : 0u) + (uint32_t)y;
-            const uint32_t first = row * (uint32_t)g.nc[0] + (uint32_t)x0;
-            const int32_t beg = cell_start[first], end = cell_start[first + (uint32_t)(x1 - x0) + 1u];
-            for (int32_t m = beg; m < end; ++m) {
-                const int32_t j = perm[m];
-                if (j <= i) continue;
-                if (!joined<DIM>(p, sorted + (int64_t)m * DIM, r2)) continue;       // p_i - p_j, i < j
-                if (FILL) key[at + found] = (unsigned long long)i * (unsigned long long)n + (unsigned long long)j;
-                ++found;
-            }
-        }
-    if (!FILL) count[i] = found;
-}
-
-// ---- sorted keys -> 1-based pair list [2, E] column-major and coords [E, dim] -------------------------------------------------
-__global__ __launch_bounds__(256) void rg_emit_kernel(int64_t E, int32_t n, int dim, const unsigned long long *__restrict__ key,
-                                                      const float *__restrict__ pts, int32_t *__restrict__ pairs,
-                                                      float *__restrict__ coords)
-{
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= E) return;
-    const unsigned long long k = key[e];
-    const int64_t i = (int64_t)(k / (unsigned long long)n), j = (int64_t)(k % (unsigned long long)n);
-    if (pairs) {
-        pairs[2 * e] = (int32_t)i + 1;
-        pairs[2 * e + 1] = (int32_t)j + 1;
-    }
-    if (coords)
-        for (int a = 0; a < dim; ++a) coords[e * dim + a] = pts[i * dim + a] - pts[j * dim + a];
-}
-
-using amp::Scratch;
-
-template <bool FILL, typename... A> void launch_neighbour(int dim, int32_t n, hipStream_t st, A... a)
-{
-    if (dim == 1) hipLaunchKernelGGL((rg_neighbour_kernel<1, FILL>), dim3(blocks(n)), dim3(256), 0, st, n, a...);
-    else if (dim == 2) hipLaunchKernelGGL((rg_neighbour_kernel<2, FILL>), dim3(blocks(n)), dim3(256), 0, st, n, a...);
-    else hipLaunchKernelGGL((rg_neighbour_kernel<3, FILL>), dim3(blocks(n)), dim3(256), 0, st, n, a...);
-}
-
-// at most kMaxCellsAxis cells per axis and 2 n in all, every cell at least radius * (1 + kCellMargin) wide; an axis whose extent
-// is below that is one cell
-Grid make_grid(const Box &box, int dim, int32_t n, float radius)
-{
-    Grid g;
-    double extent[3] = {0, 0, 0};
-    const double h = (double)radius * (1.0 + kCellMargin);
-    for (int a = 0; a < 3; ++a) {
-        g.lo[a] = a < dim ? box.lo[a] : 0.f;
-        g.nc[a] = 1;
-        if (a < dim) {
-            extent[a] = (double)box.hi[a] - (double)box.lo[a];
-            const double cells = floor(extent[a] / h);
-            g.nc[a] = cells < 1.0 ? 1 : cells > (double)kMaxCellsAxis ? kMaxCellsAxis : (int32_t)cells;
-        }
-    }
-    const int64_t cap = std::min<int64_t>(2 * (int64_t)n, (int64_t)1 << 30);
-    while ((int64_t)g.nc[0] * g.nc[1] * g.nc[2] > cap) {
-        int a = 0;
-        for (int k = 1; k < 3; ++k)
-            if (g.nc[k] > g.nc[a]) a = k;
-        g.nc[a] = (g.nc[a] + 1) / 2;
-    }
-    for (int a = 0; a < 3; ++a) g.inv_w[a] = g.nc[a] > 1 ? (float)((double)g.nc[a] / extent[a]) : 0.f;
-    return g;
-}
-
-} // namespace
-
-namespace amp {
-
-// pairs_dev / coords_dev both null: count only.  Everything on the library's stream; synchronised on return.
-int radius_pairs_core(int32_t n, int32_t dim, const float *points_dev, float radius, int32_t *pairs_dev, float *coords_dev,
-                      int64_t capacity, int64_t *n_pairs_out)
-{
-    AMP_REQUIRE(n_pairs_out != nullptr, "radius_pairs: null n_pairs_out");
-    *n_pairs_out = 0;
-    AMP_REQUIRE(dim >= 1 && dim <= 3, "radius_pairs: dim = %d outside [1,3]", dim);
-    AMP_REQUIRE(isfinite(radius) && radius > 0.f, "radius_pairs: radius = %g is not a positive finite number", (double)radius);
-    AMP_REQUIRE(n >= 0 && (n == 0 || points_dev != nullptr), "radius_pairs: bad arguments");
-    if (n == 0) return 0;
-    const float r2 = radius * radius;
-    AMP_REQUIRE(isfinite(r2), "radius_pairs: radius = %g squared is not finite in fp32", (double)radius);
-    hipStream_t st = stream();
-    const bool fill = pairs_dev != nullptr || coords_dev != nullptr;
-
-    Scratch tmp;
-    Box *d_partial = nullptr, *d_box = nullptr;
-    const int box_blocks = (int)std::min<int64_t>(kBoxBlocks, blocks(n));
-    if (tmp.get(&d_partial, box_blocks) || tmp.get(&d_box, 1)) return 1;
-    hipLaunchKernelGGL(rg_box_kernel, dim3(box_blocks), dim3(256), 0, st, n, (int)dim, points_dev, d_partial);
-    hipLaunchKernelGGL(rg_box_final_kernel, dim3(1), dim3(256), 0, st, box_blocks, (const Box *)d_partial, d_box);
-    AMP_LAUNCH_CHECK();
-    Box box;
-    AMP_HIP(hipMemcpyAsync(&box, d_box, sizeof(box), hipMemcpyDeviceToHost, st));
-    AMP_HIP(hipStreamSynchronize(st));
-    if (box.first_bad != ~0ull) {
-        float p[3] = {0.f, 0.f, 0.f};
-        AMP_HIP(hipMemcpy(p, points_dev + box.first_bad * (unsigned long long)dim, sizeof(float) * dim, hipMemcpyDeviceToHost));
-        int a = 0;
-        while (a < dim - 1 && isfinite(p[a])) ++a;
-        set_error("radius_pairs: points(%d,%llu) = %g is not finite", a + 1, box.first_bad + 1, (double)p[a]);
-        return 2;
-    }
-    const Grid grid = make_grid(box, dim, n, radius);
-    const uint32_t n_cells = (uint32_t)((int64_t)grid.nc[0] * grid.nc[1] * grid.nc[2]);
-
-    uint32_t *d_key = nullptr, *d_key_s = nullptr, *d_key_t = nullptr, *d_count = nullptr;
-    int32_t *d_perm = nullptr, *d_perm_t = nullptr, *d_cell_start = nullptr;
-    float *d_sorted = nullptr;
-    unsigned long long *d_tile = nullptr, *d_offset = nullptr;
-    void *d_temp = nullptr;
-    const uint32_t tiles = scan64::tiles(n);
-    if (tmp.get(&d_key, n) || tmp.get(&d_key_s, n) || tmp.get(&d_key_t, n) || tmp.get(&d_perm, n) || tmp.get(&d_perm_t, n) ||
-        tmp.get(&d_cell_start, (size_t)n_cells + 1) || tmp.get(&d_sorted, (size_t)n * dim) || tmp.get(&d_count, n) ||
-        tmp.get(&d_tile, (size_t)tiles + 1) || tmp.get((char **)&d_temp, radix::scratch_bytes(n)))
-        return 1;
-    hipLaunchKernelGGL(rg_cell_key_kernel, dim3(blocks(n)), dim3(256), 0, st, n, (int)dim, points_dev, grid, d_key);
-    AMP_LAUNCH_CHECK();
-    if (int rc = radix::sort_pairs<uint32_t>((const uint32_t *)d_key, nullptr, n, bits_for(n_cells - 1), d_key_s, d_perm, d_key_t, d_perm_t,
-                                             d_temp, st))
-        return rc;
-    hipLaunchKernelGGL(rg_gather_points_kernel, dim3(blocks(n)), dim3(256), 0, st, n, (int)dim, points_dev, (const int32_t *)d_perm,
-                       d_sorted);
-    hipLaunchKernelGGL(rg_cell_start_kernel, dim3(blocks((int64_t)n_cells + 1)), dim3(256), 0, st, n_cells, (const uint32_t *)d_key_s, n,
-                       d_cell_start);
-    launch_neighbour<false>(dim, n, st, grid, r2, (const float *)d_sorted, (const int32_t *)d_perm, (const uint32_t *)d_key_s,
-                            (const int32_t *)d_cell_start, d_count, (const unsigned long long *)nullptr, (unsigned long long *)nullptr);
-    hipLaunchKernelGGL(scan64::tile_sum_kernel<uint32_t>, dim3(tiles), dim3(256), 0, st, (int64_t)n, (const uint32_t *)d_count, d_tile);
-    hipLaunchKernelGGL(scan64::scan_tiles_kernel, dim3(1), dim3(256), 0, st, tiles, d_tile);
-    AMP_LAUNCH_CHECK();
-    unsigned long long total = 0;
-    AMP_HIP(hipMemcpyAsync(&total, d_tile + tiles, sizeof(total), hipMemcpyDeviceToHost, st));
-    AMP_HIP(hipStreamSynchronize(st));
-    // the limit of csr_from_edges_core, found by the count pass before anything of that size is allocated
-    AMP_REQUIRE(total < (1ull << 31) && 2 * (int64_t)total + n < (int64_t)INT32_MAX,
-                "radius_pairs: %llu pairs among %d points: more than 2^31 CSR entries", total, n);
-    *n_pairs_out = (int64_t)total;
-    if (!fill) return 0;
-    AMP_REQUIRE(capacity >= (int64_t)total, "radius_pairs: the output buffers hold %lld pairs, the graph has %lld", (long long)capacity,
-                (long long)total);
-    if (total == 0) return 0;
-
-    const int64_t E = (int64_t)total;
-    unsigned long long *d_pk = nullptr, *d_pk_s = nullptr, *d_pk_t = nullptr;
-    int32_t *d_v = nullptr, *d_v_t = nullptr;
-    void *d_temp2 = nullptr;
-    if (tmp.get(&d_offset, n) || tmp.get(&d_pk, E) || tmp.get(&d_pk_s, E) || tmp.get(&d_pk_t, E) || tmp.get(&d_v, E) || tmp.get(&d_v_t, E) ||
-        tmp.get((char **)&d_temp2, radix::scratch_bytes(E)))
-        return 1;
-    hipLaunchKernelGGL(scan64::apply_kernel<uint32_t>, dim3(tiles), dim3(256), 0, st, (int64_t)n, (const uint32_t *)d_count,
-                       (const unsigned long long *)d_tile, d_offset);
-    launch_neighbour<true>(dim, n, st, grid, r2, (const float *)d_sorted, (const int32_t *)d_perm, (const uint32_t *)d_key_s,
-                           (const int32_t *)d_cell_start, (uint32_t *)nullptr, (const unsigned long long *)d_offset, d_pk);
-    AMP_LAUNCH_CHECK();
-    // rows are already in order of i; the sort of the whole key orders the partners inside every row
-    const int key_bits = bits_for((unsigned long long)n * (unsigned long long)n - 1ull);
-    if (int rc = radix::sort_pairs<unsigned long long>((const unsigned long long *)d_pk, nullptr, E, key_bits, d_pk_s, d_v, d_pk_t, d_v_t,
-                                                       d_temp2, st))
-        return rc;
-    hipLaunchKernelGGL(rg_emit_kernel, dim3(blocks(E)), dim3(256), 0, st, E, n, (int)dim, (const unsigned long long *)d_pk_s, points_dev,
-                       pairs_dev, coords_dev);
-    AMP_LAUNCH_CHECK();
-    AMP_HIP(hipStreamSynchronize(st));   // scratch dies with this scope
-    return 0;
-}
-
-} // namespace amp
-
-extern "C" int athena_mp_radius_pairs(int32_t n, int32_t dim, const float *points_dev, float radius, int32_t *pairs_dev,
-                                      float *coords_dev, int64_t capacity, int64_t *n_pairs_out)
-{
-    return amp::radius_pairs_core(n, dim, points_dev, radius, pairs_dev, coords_dev, capacity, n_pairs_out);
-}
-
-extern "C" int athena_mp_radius_graph_host(int32_t n, int32_t dim, const float *points_host, float radius, int32_t add_self_loops,
-                                           int32_t *adj_ia_out, int32_t *adj_ja_out, int64_t capacity, int64_t *nnz_out,
-                                           float *coords_out, int64_t coords_capacity, int64_t *n_pairs_out)
-{
-    AMP_REQUIRE(nnz_out != nullptr && n_pairs_out != nullptr, "radius_graph_host: null output pointer");
-    *nnz_out = *n_pairs_out = 0;
-    AMP_REQUIRE(n >= 0 && dim >= 1 && dim <= 3 && (n == 0 || points_host != nullptr), "radius_graph_host: bad arguments (n = %d, dim = %d)",
-                n, dim);
-    hipStream_t st = amp::stream();
-    Scratch tmp;
-    float *d_pts = nullptr, *d_coords = nullptr;
-    int32_t *d_pairs = nullptr;
-    if (tmp.get(&d_pts, (size_t)n * dim)) return 1;
-    if (n > 0) AMP_HIP(hipMemcpyAsync(d_pts, points_host, sizeof(float) * (size_t)n * dim, hipMemcpyHostToDevice, st));
-    int64_t E = 0;
-    if (int rc = amp::radius_pairs_core(n, dim, d_pts, radius, nullptr, nullptr, 0, &E)) return rc;
-    // no self pair and no duplicate pair: every pair is two entries, every vertex gets its loop when asked
-    const int64_t nnz = 2 * E + (add_self_loops ? n : 0);
-    *n_pairs_out = E;
-    *nnz_out = nnz;
-    if (adj_ja_out == nullptr) return 0;                          // size query
-    AMP_REQUIRE(adj_ia_out != nullptr && (coords_out != nullptr || E == 0), "radius_graph_host: null output array");
-    AMP_REQUIRE(capacity >= nnz, "radius_graph_host: adj_ja buffer holds %lld entries, the graph has %lld", (long long)capacity,
-                (long long)nnz);
-    AMP_REQUIRE(coords_capacity >= E, "radius_graph_host: coords buffer holds %lld pairs, the graph has %lld", (long long)coords_capacity,
-                (long long)E);
-    if (tmp.get(&d_pairs, 2 * (size_t)E) || tmp.get(&d_coords, (size_t)E * dim)) return 1;
-    if (int rc = amp::radius_pairs_core(n, dim, d_pts, radius, d_pairs, d_coords, E, &E)) return rc;
-    if (E > 0) AMP_HIP(hipMemcpyAsync(coords_out, d_coords, sizeof(float) * (size_t)E * dim, hipMemcpyDeviceToHost, st));
-    int64_t nnz_built = 0;
-    if (int rc = amp::csr_from_edges_core(n, E, d_pairs, add_self_loops, adj_ia_out, adj_ja_out, capacity, &nnz_built, nullptr, true))
-        return rc;
-    AMP_HIP(hipStreamSynchronize(st));
-    *nnz_out = nnz_built;
-    return 0;
-}
-
-// ---- a batch of clouds: one block-diagonal pair list, a grid per cloud --------------------------------------------------------------
-// The definition (include/athena_mp.h): the pair lists radius_pairs_core gives for the slices points[offsets[b] : offsets[b+1]],
-// in cloud order, offsets[b] added to both indices; edge_offsets[b] = pairs whose i is below offsets[b].
-//
-// How: the host cuts the clouds into work items (cloud, points p0 .. p1-1) of at most kItemPoints points, one 64-lane wave each.
-// A bounding box per item (min and max are order-free; a wave folds with __shfl_xor and writes its own slot), folded per cloud in
-// item order; the boxes come home and make_grid runs per cloud, unchanged -- so the margin proof above holds for every cloud with
-// its own n: cells at least radius * (1 + 2^-10) wide, at most kMaxCellsAxis per axis, at most 2 m_b per cloud, at most 2 n in
-// all.  A cloud's cells are the keys [cell_base[b], cell_base[b+1]): disjoint ranges, so after the key pass no kernel sees a
-// candidate pair of two clouds.  From there on the passes are those of the single cloud over all points at once -- sort of (cell,
-// id), positions in cell order, cell starts, COUNT, 64-bit scan in point-id order, FILL, one sort, emit -- with a thread looking
-// up its cloud (the last b with offsets[b] <= i: empty clouds repeat a value and own no point) and loading that cloud's grid.
-// Both ends of a pair are in one cloud, so the key is i * M + (j - offsets[b]) with M the largest cloud: the order is that of
-// (i, j), in fewer bits than i * n + j.  No atomics on data; every access to points and coords is 4 bytes wide.
-namespace {
-
-// rg_neighbour_kernel with the grid of the slot's cloud and the walk inside that cloud's cells.
+// One thread per slot of the cell order: the point i = perm[slot] against every point j > i of the 3^DIM cells around its own,
+// with the grid of the slot's cloud and the walk inside that cloud's cells.  FILL = false: count[i] = number of partners.
 // FILL = true: key[offset[i] + t] = i * M + (j - offsets[cloud]) for the t-th partner found.
 template <int DIM, bool FILL>
 __global__ __launch_bounds__(256) void rgb_neighbour_kernel(int32_t n, int32_t B, const int32_t *__restrict__ offsets,
@@ -374,6 +124,7 @@ __global__ __launch_bounds__(256) void rgb_edge_offsets_kernel(int32_t B, int32_
     edge_offsets[b] = (long long)(v < n ? offset[v] : *total);
 }
 
+// ---- sorted keys -> 1-based pair list [2, E] column-major and coords [E, dim] -------------------------------------------------
 __global__ __launch_bounds__(256) void rgb_emit_kernel(int64_t E, int32_t B, const int32_t *__restrict__ offsets, unsigned long long M,
                                                        int dim, const unsigned long long *__restrict__ key,
                                                        const float *__restrict__ pts, int32_t *__restrict__ pairs,
@@ -392,12 +143,48 @@ __global__ __launch_bounds__(256) void rgb_emit_kernel(int64_t E, int32_t B, con
         for (int a = 0; a < dim; ++a) coords[e * dim + a] = pts[i * dim + a] - pts[j * dim + a];
 }
 
-template <bool FILL, typename... A> void launch_neighbour_batched(int dim, int32_t n, hipStream_t st, A... a)
+using amp::Scratch;
+
+template <bool FILL, typename... A> void launch_neighbour(int dim, int32_t n, hipStream_t st, A... a)
 {
     if (dim == 1) hipLaunchKernelGGL((rgb_neighbour_kernel<1, FILL>), dim3(blocks(n)), dim3(256), 0, st, n, a...);
     else if (dim == 2) hipLaunchKernelGGL((rgb_neighbour_kernel<2, FILL>), dim3(blocks(n)), dim3(256), 0, st, n, a...);
     else hipLaunchKernelGGL((rgb_neighbour_kernel<3, FILL>), dim3(blocks(n)), dim3(256), 0, st, n, a...);
 }
+
+// at most kMaxCellsAxis cells per axis and 2 n in all, every cell at least radius * (1 + kCellMargin) wide; an axis whose extent
+// is below that is one cell
+Grid make_grid(const Box &box, int dim, int32_t n, float radius)
+{
+    Grid g;
+    double extent[3] = {0, 0, 0};
+    const double h = (double)radius * (1.0 + kCellMargin);
+    for (int a = 0; a < 3; ++a) {
+        g.lo[a] = a < dim ? box.lo[a] : 0.f;
+        g.nc[a] = 1;
+        if (a < dim) {
+            extent[a] = (double)box.hi[a] - (double)box.lo[a];
+            const double cells = floor(extent[a] / h);
+            g.nc[a] = cells < 1.0 ? 1 : cells > (double)kMaxCellsAxis ? kMaxCellsAxis : (int32_t)cells;
+        }
+    }
+    const int64_t cap = std::min<int64_t>(2 * (int64_t)n, (int64_t)1 << 30);
+    while ((int64_t)g.nc[0] * g.nc[1] * g.nc[2] > cap) {
+        int a = 0;
+        for (int k = 1; k < 3; ++k)
+            if (g.nc[k] > g.nc[a]) a = k;
+        g.nc[a] = (g.nc[a] + 1) / 2;
+    }
+    for (int a = 0; a < 3; ++a) g.inv_w[a] = g.nc[a] > 1 ? (float)((double)g.nc[a] / extent[a]) : 0.f;
+    return g;
+}
+
+// how an entry speaks of itself in its messages: its name, what it calls its result, and whether it has clouds to name
+struct Caller {
+    const char *who, *noun;
+    bool names_clouds;
+};
+constexpr Caller kSingle = {"radius_pairs", "graph", false}, kBatched = {"radius_pairs_batched", "batch", true};
 
 // the checks both batched entries make before anything touches the device: 0, or 2 with the message set
 int batch_arguments_check(const char *who, int32_t B, const int32_t *offsets, int32_t dim, float radius)
@@ -414,15 +201,16 @@ namespace amp {
 
 // pairs_dev / coords_dev both null: count only (edge_offsets_out is filled either way).  Everything on the library's stream;
 // synchronised on return.
-int radius_pairs_batched_core(int32_t B, int32_t n, const int32_t *offsets, int32_t dim, const float *points_dev, float radius,
-                              int32_t *pairs_dev, float *coords_dev, int64_t capacity, int64_t *edge_offsets_out, int64_t *n_pairs_out)
+int radius_pairs_batched_core(const Caller &c, int32_t B, int32_t n, const int32_t *offsets, int32_t dim, const float *points_dev,
+                              float radius, int32_t *pairs_dev, float *coords_dev, int64_t capacity, int64_t *edge_offsets_out,
+                              int64_t *n_pairs_out)
 {
-    static const char who[] = "radius_pairs_batched";
-    AMP_REQUIRE(n_pairs_out != nullptr, "radius_pairs_batched: null n_pairs_out");
+    const char *who = c.who;
+    AMP_REQUIRE(n_pairs_out != nullptr, "%s: null n_pairs_out", who);
     *n_pairs_out = 0;
     if (int rc = batch_arguments_check(who, B, offsets, dim, radius)) return rc;
-    AMP_REQUIRE(offsets[B] == n, "radius_pairs_batched: offsets end at %d, the batch has %d points", offsets[B], n);
-    AMP_REQUIRE(n == 0 || points_dev != nullptr, "radius_pairs_batched: null points");
+    AMP_REQUIRE(offsets[B] == n, "%s: offsets end at %d, the batch has %d points", who, offsets[B], n);
+    AMP_REQUIRE(n == 0 || points_dev != nullptr, "%s: null points", who);
     if (edge_offsets_out) std::fill(edge_offsets_out, edge_offsets_out + B + 1, (int64_t)0);
     if (n == 0) return 0;
     const float r2 = radius * radius;
@@ -430,80 +218,38 @@ int radius_pairs_batched_core(int32_t B, int32_t n, const int32_t *offsets, int3
     const bool fill = pairs_dev != nullptr || coords_dev != nullptr;
 
     Scratch tmp;
-    BatchItems it;
-    std::vector<Box> box;
-    if (int rc = batch_boxes(who, B, offsets, dim, points_dev, st, tmp, it, box)) return rc;
-    const int32_t W = it.W, m_max = it.m_max;
-    const int32_t *d_items = it.d_items, *d_off = it.d_off;
-    const unsigned item_blocks = it.item_blocks;
+    CellGrid cg;
+    if (int rc = build_cell_grid(who, c.names_clouds, B, n, offsets, dim, points_dev, st, tmp,
+                                 [&](const Box &box, int32_t m, int32_t) { return make_grid(box, dim, m, radius); }, cg))
+        return rc;
+    const int32_t *d_off = cg.it.d_off;
 
-    // a grid per non-empty cloud; cell_base = the exclusive sum of the clouds' cell counts (an empty cloud adds 0)
-    std::vector<Grid> grids((size_t)B);
-    std::vector<uint32_t> cell_base((size_t)B + 1);
-    int64_t total_cells = 0;
-    for (int32_t b = 0; b < B; ++b) {
-        cell_base[b] = (uint32_t)total_cells;
-        const int32_t m = offsets[b + 1] - offsets[b];
-        if (m == 0) {
-            grids[b] = Grid{};
-            continue;
-        }
-        grids[b] = make_grid(box[b], dim, m, radius);
-        total_cells += (int64_t)grids[b].nc[0] * grids[b].nc[1] * grids[b].nc[2];
-        AMP_REQUIRE(total_cells < (int64_t)INT32_MAX, "radius_pairs_batched: more than 2^31 grid cells over %d points", n);
-    }
-    cell_base[B] = (uint32_t)total_cells;
-    const uint32_t n_cells = (uint32_t)total_cells;
-
-    Grid *d_grids = nullptr;
-    uint32_t *d_cell_base = nullptr, *d_key = nullptr, *d_key_s = nullptr, *d_key_t = nullptr, *d_count = nullptr;
-    int32_t *d_perm = nullptr, *d_perm_t = nullptr, *d_cell_start = nullptr;
-    float *d_sorted = nullptr;
+    uint32_t *d_count = nullptr;
     unsigned long long *d_tile = nullptr, *d_offset = nullptr;
     long long *d_edge_off = nullptr;
-    void *d_temp = nullptr;
-    const uint32_t tiles = scan64::tiles(n);
-    if (tmp.get(&d_grids, B) || tmp.get(&d_cell_base, (size_t)B + 1) || tmp.get(&d_key, n) || tmp.get(&d_key_s, n) ||
-        tmp.get(&d_key_t, n) || tmp.get(&d_perm, n) || tmp.get(&d_perm_t, n) || tmp.get(&d_cell_start, (size_t)n_cells + 1) ||
-        tmp.get(&d_sorted, (size_t)n * dim) || tmp.get(&d_count, n) || tmp.get(&d_tile, (size_t)tiles + 1) || tmp.get(&d_offset, n) ||
-        tmp.get(&d_edge_off, (size_t)B + 1) || tmp.get((char **)&d_temp, radix::scratch_bytes(n)))
+    if (tmp.get(&d_count, n) || tmp.get(&d_tile, (size_t)scan64::tiles(n) + 1) || tmp.get(&d_offset, n) ||
+        tmp.get(&d_edge_off, (size_t)B + 1))
         return 1;
-    AMP_HIP(hipMemcpyAsync(d_grids, grids.data(), sizeof(Grid) * (size_t)B, hipMemcpyHostToDevice, st));
-    AMP_HIP(hipMemcpyAsync(d_cell_base, cell_base.data(), sizeof(uint32_t) * ((size_t)B + 1), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(rgb_cell_key_kernel, dim3(item_blocks), dim3(64 * kItemWaves), 0, st, W, (const int32_t *)d_items, (int)dim,
-                       points_dev, (const Grid *)d_grids, (const uint32_t *)d_cell_base, d_key);
-    AMP_LAUNCH_CHECK();
-    if (int rc = radix::sort_pairs<uint32_t>((const uint32_t *)d_key, nullptr, n, bits_for(n_cells - 1), d_key_s, d_perm, d_key_t, d_perm_t,
-                                             d_temp, st))
-        return rc;
-    hipLaunchKernelGGL(rg_gather_points_kernel, dim3(blocks(n)), dim3(256), 0, st, n, (int)dim, points_dev, (const int32_t *)d_perm,
-                       d_sorted);
-    hipLaunchKernelGGL(rg_cell_start_kernel, dim3(blocks((int64_t)n_cells + 1)), dim3(256), 0, st, n_cells, (const uint32_t *)d_key_s, n,
-                       d_cell_start);
-    const unsigned long long M = (unsigned long long)m_max;
-    launch_neighbour_batched<false>(dim, n, st, B, (const int32_t *)d_off, (const Grid *)d_grids, (const uint32_t *)d_cell_base, M, r2,
-                                    (const float *)d_sorted, (const int32_t *)d_perm, (const uint32_t *)d_key_s,
-                                    (const int32_t *)d_cell_start, d_count, (const unsigned long long *)nullptr,
-                                    (unsigned long long *)nullptr);
-    hipLaunchKernelGGL(scan64::tile_sum_kernel<uint32_t>, dim3(tiles), dim3(256), 0, st, (int64_t)n, (const uint32_t *)d_count, d_tile);
-    hipLaunchKernelGGL(scan64::scan_tiles_kernel, dim3(1), dim3(256), 0, st, tiles, d_tile);
-    hipLaunchKernelGGL(scan64::apply_kernel<uint32_t>, dim3(tiles), dim3(256), 0, st, (int64_t)n, (const uint32_t *)d_count,
-                       (const unsigned long long *)d_tile, d_offset);
-    hipLaunchKernelGGL(rgb_edge_offsets_kernel, dim3(blocks((int64_t)B + 1)), dim3(256), 0, st, B, n, (const int32_t *)d_off,
-                       (const unsigned long long *)d_offset, (const unsigned long long *)(d_tile + tiles), d_edge_off);
+    const unsigned long long M = (unsigned long long)cg.it.m_max;
+    launch_neighbour<false>(dim, n, st, B, d_off, (const Grid *)cg.d_grids, (const uint32_t *)cg.d_cell_base, M, r2,
+                            (const float *)cg.d_sorted, (const int32_t *)cg.d_perm, (const uint32_t *)cg.d_key_s,
+                            (const int32_t *)cg.d_cell_start, d_count, (const unsigned long long *)nullptr, (unsigned long long *)nullptr);
+    const unsigned long long *d_total = scan64::exclusive(n, (const uint32_t *)d_count, d_tile, d_offset, st);
+    hipLaunchKernelGGL(rgb_edge_offsets_kernel, dim3(blocks((int64_t)B + 1)), dim3(256), 0, st, B, n, d_off,
+                       (const unsigned long long *)d_offset, d_total, d_edge_off);
     AMP_LAUNCH_CHECK();
     unsigned long long total = 0;
-    AMP_HIP(hipMemcpyAsync(&total, d_tile + tiles, sizeof(total), hipMemcpyDeviceToHost, st));
+    AMP_HIP(hipMemcpyAsync(&total, d_total, sizeof(total), hipMemcpyDeviceToHost, st));
     if (edge_offsets_out)
         AMP_HIP(hipMemcpyAsync(edge_offsets_out, d_edge_off, sizeof(int64_t) * ((size_t)B + 1), hipMemcpyDeviceToHost, st));
     AMP_HIP(hipStreamSynchronize(st));
     // the limit of csr_from_edges_core, found by the count pass before anything of that size is allocated
     AMP_REQUIRE(total < (1ull << 31) && 2 * (int64_t)total + n < (int64_t)INT32_MAX,
-                "radius_pairs_batched: %llu pairs among %d points: more than 2^31 CSR entries", total, n);
+                "%s: %llu pairs among %d points: more than 2^31 CSR entries", who, total, n);
     *n_pairs_out = (int64_t)total;
     if (!fill) return 0;
-    AMP_REQUIRE(capacity >= (int64_t)total, "radius_pairs_batched: the output buffers hold %lld pairs, the batch has %lld",
-                (long long)capacity, (long long)total);
+    AMP_REQUIRE(capacity >= (int64_t)total, "%s: the output buffers hold %lld pairs, the %s has %lld", who, (long long)capacity, c.noun,
+                (long long)total);
     if (total == 0) return 0;
 
     const int64_t E = (int64_t)total;
@@ -513,29 +259,72 @@ int radius_pairs_batched_core(int32_t B, int32_t n, const int32_t *offsets, int3
     if (tmp.get(&d_pk, E) || tmp.get(&d_pk_s, E) || tmp.get(&d_pk_t, E) || tmp.get(&d_v, E) || tmp.get(&d_v_t, E) ||
         tmp.get((char **)&d_temp2, radix::scratch_bytes(E)))
         return 1;
-    launch_neighbour_batched<true>(dim, n, st, B, (const int32_t *)d_off, (const Grid *)d_grids, (const uint32_t *)d_cell_base, M, r2,
-                                   (const float *)d_sorted, (const int32_t *)d_perm, (const uint32_t *)d_key_s,
-                                   (const int32_t *)d_cell_start, (uint32_t *)nullptr, (const unsigned long long *)d_offset, d_pk);
+    launch_neighbour<true>(dim, n, st, B, d_off, (const Grid *)cg.d_grids, (const uint32_t *)cg.d_cell_base, M, r2,
+                           (const float *)cg.d_sorted, (const int32_t *)cg.d_perm, (const uint32_t *)cg.d_key_s,
+                           (const int32_t *)cg.d_cell_start, (uint32_t *)nullptr, (const unsigned long long *)d_offset, d_pk);
     AMP_LAUNCH_CHECK();
     // rows are already in order of i; the sort of the whole key orders the partners inside every row
     const int key_bits = bits_for((unsigned long long)n * M - 1ull);
     if (int rc = radix::sort_pairs<unsigned long long>((const unsigned long long *)d_pk, nullptr, E, key_bits, d_pk_s, d_v, d_pk_t, d_v_t,
                                                        d_temp2, st))
         return rc;
-    hipLaunchKernelGGL(rgb_emit_kernel, dim3(blocks(E)), dim3(256), 0, st, E, B, (const int32_t *)d_off, M, (int)dim,
-                       (const unsigned long long *)d_pk_s, points_dev, pairs_dev, coords_dev);
+    hipLaunchKernelGGL(rgb_emit_kernel, dim3(blocks(E)), dim3(256), 0, st, E, B, d_off, M, (int)dim, (const unsigned long long *)d_pk_s,
+                       points_dev, pairs_dev, coords_dev);
     AMP_LAUNCH_CHECK();
     AMP_HIP(hipStreamSynchronize(st));   // scratch dies with this scope
     return 0;
 }
 
+// One cloud: the checks of the single-cloud entries, in their order, then a batch of one.  n = 0 returns before the square of
+// the radius is looked at, as it always did.
+int radius_pairs_core(int32_t n, int32_t dim, const float *points_dev, float radius, int32_t *pairs_dev, float *coords_dev,
+                      int64_t capacity, int64_t *n_pairs_out)
+{
+    AMP_REQUIRE(n_pairs_out != nullptr, "radius_pairs: null n_pairs_out");
+    *n_pairs_out = 0;
+    AMP_REQUIRE(dim >= 1 && dim <= 3, "radius_pairs: dim = %d outside [1,3]", dim);
+    AMP_REQUIRE(isfinite(radius) && radius > 0.f, "radius_pairs: radius = %g is not a positive finite number", (double)radius);
+    AMP_REQUIRE(n >= 0 && (n == 0 || points_dev != nullptr), "radius_pairs: bad arguments");
+    if (n == 0) return 0;
+    const int32_t offsets[2] = {0, n};
+    return radius_pairs_batched_core(kSingle, 1, n, offsets, dim, points_dev, radius, pairs_dev, coords_dev, capacity, nullptr, n_pairs_out);
+}
+
 } // namespace amp
+
+extern "C" int athena_mp_radius_pairs(int32_t n, int32_t dim, const float *points_dev, float radius, int32_t *pairs_dev,
+                                      float *coords_dev, int64_t capacity, int64_t *n_pairs_out)
+{
+    return amp::radius_pairs_core(n, dim, points_dev, radius, pairs_dev, coords_dev, capacity, n_pairs_out);
+}
+
+extern "C" int athena_mp_radius_graph_host(int32_t n, int32_t dim, const float *points_host, float radius, int32_t add_self_loops,
+                                           int32_t *adj_ia_out, int32_t *adj_ja_out, int64_t capacity, int64_t *nnz_out,
+                                           float *coords_out, int64_t coords_capacity, int64_t *n_pairs_out)
+{
+    AMP_REQUIRE(nnz_out != nullptr && n_pairs_out != nullptr, "radius_graph_host: null output pointer");
+    *nnz_out = *n_pairs_out = 0;
+    AMP_REQUIRE(n >= 0 && dim >= 1 && dim <= 3 && (n == 0 || points_host != nullptr), "radius_graph_host: bad arguments (n = %d, dim = %d)",
+                n, dim);
+    hipStream_t st = amp::stream();
+    Scratch tmp;
+    float *d_pts = nullptr;
+    if (tmp.get(&d_pts, (size_t)n * dim)) return 1;
+    if (n > 0) AMP_HIP(hipMemcpyAsync(d_pts, points_host, sizeof(float) * (size_t)n * dim, hipMemcpyHostToDevice, st));
+    int64_t E = 0;
+    if (int rc = amp::radius_pairs_core(n, dim, d_pts, radius, nullptr, nullptr, 0, &E)) return rc;
+    return amp::graph_host_tail("radius_graph_host", n, dim, E, add_self_loops, adj_ia_out, adj_ja_out, capacity, nnz_out, coords_out,
+                           coords_capacity, n_pairs_out, st, [&](int32_t **d_pairs, float **d_coords) {
+                               if (tmp.get(d_pairs, 2 * (size_t)E) || tmp.get(d_coords, (size_t)E * dim)) return 1;
+                               return amp::radius_pairs_core(n, dim, d_pts, radius, *d_pairs, *d_coords, E, &E);
+                           });
+}
 
 extern "C" int athena_mp_radius_pairs_batched(int32_t n_clouds, int32_t n, const int32_t *offsets_host, int32_t dim,
                                               const float *points_dev, float radius, int32_t *pairs_dev, float *coords_dev,
                                               int64_t capacity, int64_t *edge_offsets_host, int64_t *n_pairs_out)
 {
-    return amp::radius_pairs_batched_core(n_clouds, n, offsets_host, dim, points_dev, radius, pairs_dev, coords_dev, capacity,
+    return amp::radius_pairs_batched_core(kBatched, n_clouds, n, offsets_host, dim, points_dev, radius, pairs_dev, coords_dev, capacity,
                                           edge_offsets_host, n_pairs_out);
 }
 
@@ -551,31 +340,17 @@ extern "C" int athena_mp_radius_graph_batched_host(int32_t n_clouds, int32_t n, 
     if (int rc = batch_arguments_check("radius_graph_batched_host", n_clouds, offsets_host, dim, radius)) return rc;
     hipStream_t st = amp::stream();
     Scratch tmp;
-    float *d_pts = nullptr, *d_coords = nullptr;
-    int32_t *d_pairs = nullptr;
+    float *d_pts = nullptr;
     if (tmp.get(&d_pts, (size_t)n * dim)) return 1;
     if (n > 0) AMP_HIP(hipMemcpyAsync(d_pts, points_host, sizeof(float) * (size_t)n * dim, hipMemcpyHostToDevice, st));
     int64_t E = 0;
-    if (int rc = amp::radius_pairs_batched_core(n_clouds, n, offsets_host, dim, d_pts, radius, nullptr, nullptr, 0, edge_offsets_out, &E))
+    if (int rc = amp::radius_pairs_batched_core(kBatched, n_clouds, n, offsets_host, dim, d_pts, radius, nullptr, nullptr, 0,
+                                                edge_offsets_out, &E))
         return rc;
-    // no self pair and no duplicate pair: every pair is two entries, every vertex gets its loop when asked
-    const int64_t nnz = 2 * E + (add_self_loops ? n : 0);
-    *n_pairs_out = E;
-    *nnz_out = nnz;
-    if (adj_ja_out == nullptr) return 0;                          // size query
-    AMP_REQUIRE(adj_ia_out != nullptr && (coords_out != nullptr || E == 0), "radius_graph_batched_host: null output array");
-    AMP_REQUIRE(capacity >= nnz, "radius_graph_batched_host: adj_ja buffer holds %lld entries, the graph has %lld", (long long)capacity,
-                (long long)nnz);
-    AMP_REQUIRE(coords_capacity >= E, "radius_graph_batched_host: coords buffer holds %lld pairs, the graph has %lld",
-                (long long)coords_capacity, (long long)E);
-    if (tmp.get(&d_pairs, 2 * (size_t)E) || tmp.get(&d_coords, (size_t)E * dim)) return 1;
-    if (int rc = amp::radius_pairs_batched_core(n_clouds, n, offsets_host, dim, d_pts, radius, d_pairs, d_coords, E, edge_offsets_out, &E))
-        return rc;
-    if (E > 0) AMP_HIP(hipMemcpyAsync(coords_out, d_coords, sizeof(float) * (size_t)E * dim, hipMemcpyDeviceToHost, st));
-    int64_t nnz_built = 0;
-    if (int rc = amp::csr_from_edges_core(n, E, d_pairs, add_self_loops, adj_ia_out, adj_ja_out, capacity, &nnz_built, nullptr, true))
-        return rc;
-    AMP_HIP(hipStreamSynchronize(st));
-    *nnz_out = nnz_built;
-    return 0;
+    return amp::graph_host_tail("radius_graph_batched_host", n, dim, E, add_self_loops, adj_ia_out, adj_ja_out, capacity, nnz_out, coords_out,
+                           coords_capacity, n_pairs_out, st, [&](int32_t **d_pairs, float **d_coords) {
+                               if (tmp.get(d_pairs, 2 * (size_t)E) || tmp.get(d_coords, (size_t)E * dim)) return 1;
+                               return amp::radius_pairs_batched_core(kBatched, n_clouds, n, offsets_host, dim, d_pts, radius, *d_pairs,
+                                                                     *d_coords, E, edge_offsets_out, &E);
+                           });
 }

@@ -1,6 +1,7 @@
 // Exclusive scan of n counts into 64-bit offsets, in index order: tile sums, one block that scans the tiles, one pass that
-// applies them.  Deterministic (no atomics).  Included by radius_graph.hip (counts per point) and periodic_graph.hip (counts per
-// work item); the kernels are templates or static, one copy per file.
+// applies them; exclusive() launches the three.  Deterministic (no atomics).  Included by radius_graph.hip (counts per point),
+// knn_graph.hip (flags per key) and periodic_graph.hip (counts per grid atom and per work item); the kernels are templates or
+// static, one copy per file.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -81,6 +82,18 @@ __global__ __launch_bounds__(256) void apply_kernel(int64_t n, const C *__restri
         if (base + k < n) offset[base + k] = run;
         run += c[k];
     }
+}
+
+// The three passes on stream st: offset[i] = count[0] + ... + count[i - 1], i < n.  tile_sum holds tiles(n) + 1 words; the grand
+// total is left in the last of them, and that device address is returned.
+template <typename C>
+inline const unsigned long long *exclusive(int64_t n, const C *count, unsigned long long *tile_sum, unsigned long long *offset, hipStream_t st)
+{
+    const uint32_t t = tiles(n);
+    hipLaunchKernelGGL(tile_sum_kernel<C>, dim3(t), dim3(256), 0, st, n, count, tile_sum);
+    hipLaunchKernelGGL(scan_tiles_kernel, dim3(1), dim3(256), 0, st, t, tile_sum);
+    hipLaunchKernelGGL(apply_kernel<C>, dim3(t), dim3(256), 0, st, n, count, (const unsigned long long *)tile_sum, offset);
+    return tile_sum + t;
 }
 
 } // namespace scan64

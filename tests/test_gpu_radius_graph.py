@@ -72,6 +72,16 @@ def test_radius_pairs_uniform_clouds(dev, n, dim, deg):
 
 
 @pytest.mark.parametrize("dim", [1, 2, 3])
+@pytest.mark.parametrize("n", [4095, 4096, 4097, 8192, 8193])
+def test_radius_pairs_at_the_work_item_edges(dev, n, dim):
+    """one cloud is a batch of one; its cell keys are written by one wave per work item of 4 096 points (cell_grid.h): one item
+    less a point, exactly one, one and a point, exactly two, two and a point.  _gpu_pairs holds the count-only call against the
+    fill."""
+    p = _rng(7 * n + dim).random((n, dim)).astype(np.float32)
+    _check(dev, p, degree_radius(n, 6.0, dim), min_pairs=n)
+
+
+@pytest.mark.parametrize("dim", [1, 2, 3])
 def test_radius_pairs_counts_on_both_sides_of_the_radix_tiles(dev, dim):
     """pair counts around one and two 4 096-entry tiles of the radix passes (radix_sort.h), chosen from the sorted fp32
     squared distances of the cloud"""
@@ -184,6 +194,47 @@ def test_radius_pairs_refuses_bad_input_and_stays_usable(dev):
     torch.cuda.synchronize()
     assert free0 - torch.cuda.mem_get_info()[0] < 8 << 20
     _check(dev, p, r)                                                      # the library is usable afterwards
+
+
+@pytest.mark.parametrize("bad,first", [({8500: (0, np.nan), 4096: (1, np.inf)}, (4096, 1, "inf")),
+                                       ({4096: (0, np.nan), 4095: (2, -np.inf)}, (4095, 2, "-inf"))])
+def test_radius_pairs_names_the_first_non_finite_point_across_work_items(dev, bad, first):
+    """bad points 4 400 apart, and on both sides of index 4 096.  One cloud alone takes its box and validity from block partials
+    (rg_box_kernel: a block strides over the cloud, so the bad points fall to different threads and blocks; 4 096 is where a
+    batch of more clouds would cut its work items), and the pipeline behind it is the batched one.  The message is the
+    single-cloud one: the smallest index and its first bad component, 1-based, and no cloud."""
+    import re
+
+    import torch
+    from athena_amd import _capi
+
+    p = _rng(15).random((9000, 3)).astype(np.float32)
+    r = degree_radius(9000, 6.0, 3)
+    q = p.copy()
+    for i, (a, v) in bad.items():
+        q[i, a] = v
+        q[i, 2] = v if a < 2 else q[i, 2]                                 # a later component of the same point: the FIRST is named
+    i, a, text = first
+    with pytest.raises(_capi.AthenaMPError) as err:
+        _query(torch.from_numpy(q).to(dev), r)
+    msg = str(err.value).split(": ", 1)[1]
+    assert re.fullmatch(r"radius_pairs: points\(%d,%d\) = .* is not finite" % (a + 1, i + 1), msg), msg
+    assert msg == "radius_pairs: points(%d,%d) = %s is not finite" % (a + 1, i + 1, text) and "cloud" not in str(err.value)
+    _check(dev, p, r, min_pairs=9000)                                      # a valid call afterwards succeeds
+
+
+def test_radius_pairs_of_no_points_and_a_radius_whose_square_overflows(dev):
+    """n = 0 returns before the square of the radius is looked at in the single-cloud entry; the batched entry checks its
+    arguments first and refuses"""
+    import torch
+    from athena_amd import _capi
+
+    none = torch.zeros((0, 3), dtype=torch.float32, device=dev)
+    assert _query(none, 1e30) == 0
+    E, off = C.c_int64(-1), np.zeros(2, np.int32)
+    with pytest.raises(_capi.AthenaMPError, match=r"radius_pairs_batched: radius = .* squared is not finite in fp32"):
+        _capi.call("athena_mp_radius_pairs_batched", 1, 0, off.ctypes.data_as(C.c_void_p), 3, None, 1e30, None, None, 0, None, C.byref(E))
+    assert E.value == 0
 
 
 def _same(a, b):
