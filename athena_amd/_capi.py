@@ -44,6 +44,9 @@ _PROTOS = {
     "athena_mp_radius_graph_host": [_i32, _i32, _vp, _f32, _i32, _vp, _vp, _i64, _vp, _vp, _i64, _vp],
     "athena_mp_radius_pairs_batched": [_i32, _i32, _vp, _i32, _vp, _f32, _vp, _vp, _i64, _vp, _vp],
     "athena_mp_radius_graph_batched_host": [_i32, _i32, _vp, _i32, _vp, _f32, _i32, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp],
+    "athena_mp_radius_pairs_bipartite": [_i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _f32, _vp, _vp, _i64, _vp, _vp, _vp],
+    "athena_mp_graph_create_bipartite_dev": [_i32, _i32, _i64, _vp, _vp, _vp, _i64, C.POINTER(_vp)],
+    "athena_mp_radius_graph_bipartite_host": [_i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _f32, _vp, _vp, _i64, _vp, _i64, _vp, _vp],
     "athena_mp_knn_pairs_batched": [_i32, _i32, _vp, _i32, _vp, _i32, _f32, _i32, _vp, _vp, _vp, _i64, _vp, _vp],
     "athena_mp_knn_pairs": [_i32, _i32, _vp, _i32, _f32, _i32, _vp, _vp, _vp, _i64, _vp],
     "athena_mp_knn_graph_batched_host": [_i32, _i32, _vp, _i32, _vp, _i32, _f32, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp],
@@ -55,6 +58,8 @@ _PROTOS = {
     "athena_mp_edge_grad_to_points": [_vp, _i32, _vp, _vp],
     "athena_mp_periodic_grad": [_vp, _i32, _i32, _vp, _vp, _vp, _f32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp],
     "athena_mp_edge_grad_to_points_host": [_vp, _i32, _vp, _vp],
+    "athena_mp_edge_grad_to_point_sets": [_vp, _i32, _vp, _vp, _vp],
+    "athena_mp_edge_grad_to_point_sets_host": [_vp, _i32, _vp, _vp, _vp],
     "athena_mp_periodic_grad_host": [_vp, _i32, _i32, _vp, _vp, _vp, _f32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp],
     "athena_mp_graph_export": [_vp, _i32, _vp, _i64, _vp],
     "athena_mp_graph_destroy": [_vp],
@@ -89,6 +94,7 @@ _PROTOS = {
     "athena_mp_activation_fwd": [_i32, _i64, _vp, _vp],
     "athena_mp_activation_bwd": [_i32, _i64, _vp, _vp, _vp],
     "athena_mp_axpy": [_i64, _f32, _vp, _vp],
+    "athena_mp_add_row_bias": [_i64, _i32, _vp, _vp],
     "athena_mp_device_copy": [_vp, _vp, C.c_uint64],
     "athena_mp_duvenaud_propagate_fwd": [_vp, _i32, _i32, _vp, _vp, _vp],
     "athena_mp_duvenaud_propagate_bwd_x": [_vp, _i32, _i32, _vp, _vp],

@@ -423,6 +423,28 @@ int athena_mp_graph_create_from_edges_dev(int32_t n_vertices, int64_t n_pairs, c
                                  capacity, nnz_out, out);
 }
 
+/* a pair list between two point sets that is already in HBM (athena_mp_radius_pairs_bipartite) -> the directed rectangular
+ * handle: pair e is the one CSR entry (row i, column j, edge id e); the degrees are the row and column lengths.  What
+ * athena_mp_graph_create builds from the same CSR with those degrees, array for array (it IS that builder, fed from HBM). */
+int athena_mp_graph_create_bipartite_dev(int32_t n_rows, int32_t n_cols, int64_t n_pairs, const int32_t *pairs_dev,
+                                         int32_t *adj_ia_out, int32_t *adj_ja_out, int64_t capacity, athena_mp_graph **out)
+{
+    AMP_REQUIRE(out != nullptr && adj_ia_out != nullptr, "graph_create_bipartite: null output pointer");
+    *out = nullptr;
+    int32_t *ja_dev = nullptr;
+    std::vector<int32_t> row_deg, col_deg;
+    int rc = amp::bipartite_csr_from_pairs("graph_create_bipartite", n_rows, n_cols, n_pairs, pairs_dev, adj_ia_out, adj_ja_out, capacity,
+                                           &ja_dev, &row_deg, &col_deg);
+    if (rc == 0) {
+        row_deg.push_back(0);   // data() of an empty vector may be null, and null degrees mean "a square graph's own"
+        col_deg.push_back(0);
+        rc = graph_create_impl(n_rows, n_cols, n_pairs, adj_ia_out, adj_ja_out, ja_dev, (int32_t)n_pairs, row_deg.data(), col_deg.data(),
+                               out);
+    }
+    if (ja_dev) (void)hipFree(ja_dev);
+    return rc;
+}
+
 static int graph_create_body(int32_t n_rows, int32_t n_cols, int64_t nnz, const int32_t *adj_ia,
                              const int32_t *adj_ja, const int32_t *adj_ja_dev, int32_t n_edge_cols,
                              const int32_t *row_deg, const int32_t *col_deg, athena_mp_graph **out);

@@ -220,10 +220,10 @@ struct BatchItems {
 };
 
 // items, their upload, and the bounding box of every cloud brought home; a non-finite coordinate is refused here, naming the
-// cloud (an entry that takes one cloud has none to name: name_cloud = false), component and point of the first one.  n > 0.
-// Synchronises the stream.
+// cloud (an entry that takes one cloud has none to name: name_cloud = false), component and point of the first one; `what` is what
+// the entry calls the array.  n > 0.  Synchronises the stream.
 inline int batch_boxes(const char *who, bool name_cloud, int32_t B, const int32_t *offsets, int32_t dim, const float *points_dev,
-                       hipStream_t st, amp::Scratch &tmp, BatchItems &it, std::vector<Box> &box)
+                       hipStream_t st, amp::Scratch &tmp, BatchItems &it, std::vector<Box> &box, const char *what = "points")
 {
     it.item_first.resize((size_t)B + 1);
     for (int32_t b = 0; b < B; ++b) {
@@ -270,9 +270,9 @@ inline int batch_boxes(const char *who, bool name_cloud, int32_t B, const int32_
         int a = 0;
         while (a < dim - 1 && isfinite(p[a])) ++a;
         if (name_cloud)
-            amp::set_error("%s: cloud %d: points(%d,%llu) = %g is not finite", who, bad_cloud + 1, a + 1, first_bad + 1, (double)p[a]);
+            amp::set_error("%s: cloud %d: %s(%d,%llu) = %g is not finite", who, bad_cloud + 1, what, a + 1, first_bad + 1, (double)p[a]);
         else
-            amp::set_error("%s: points(%d,%llu) = %g is not finite", who, a + 1, first_bad + 1, (double)p[a]);
+            amp::set_error("%s: %s(%d,%llu) = %g is not finite", who, what, a + 1, first_bad + 1, (double)p[a]);
         return 2;
     }
     return 0;
@@ -297,10 +297,10 @@ struct CellGrid {
 // gather, the cell starts.  Everything lives in tmp.  Synchronises the stream once, for the boxes.
 template <typename Make>
 int build_cell_grid(const char *who, bool name_cloud, int32_t B, int32_t n, const int32_t *offsets, int32_t dim, const float *points_dev,
-                    hipStream_t st, amp::Scratch &tmp, Make make, CellGrid &cg)
+                    hipStream_t st, amp::Scratch &tmp, Make make, CellGrid &cg, const char *what = "points")
 {
     std::vector<Box> box;
-    if (int rc = batch_boxes(who, name_cloud, B, offsets, dim, points_dev, st, tmp, cg.it, box)) return rc;
+    if (int rc = batch_boxes(who, name_cloud, B, offsets, dim, points_dev, st, tmp, cg.it, box, what)) return rc;
     std::vector<Grid> grids((size_t)B);
     std::vector<uint32_t> cell_base((size_t)B + 1);
     int64_t total_cells = 0;

@@ -166,6 +166,10 @@ int graph_build_device(athena_mp_graph *g, const int32_t *adj_ja, const std::vec
 int csr_from_edges_core(int32_t n_vertices, int64_t n_pairs, const int32_t *index_list, int32_t add_self_loops,
                         int32_t *adj_ia_out, int32_t *adj_ja_out, int64_t capacity, int64_t *nnz_out,
                         int32_t **keep_ja_dev, bool list_on_device = false);
+// a pair list between two point sets, strictly ascending in (i, j), in HBM -> its directed CSR and degrees (bipartite_graph.hip)
+int bipartite_csr_from_pairs(const char *who, int32_t n_rows, int32_t n_cols, int64_t n_pairs, const int32_t *pairs_dev,
+                             int32_t *adj_ia_out, int32_t *adj_ja_out, int64_t capacity, int32_t **ja_dev, std::vector<int32_t> *row_deg,
+                             std::vector<int32_t> *col_deg);
 // The end of a point-cloud *_graph_host entry (radius_graph.hip, knn_graph.hip) once the pair count E is known: the sizes out,
 // the size query's return, the capacity checks, then pairs(&d_pairs, &d_coords) -- the E pairs [2, E] and coords [E, dim] on the
 // device, built or already there -- the coords home and the CSR through csr_from_edges_core.
@@ -196,6 +200,7 @@ int graph_host_tail(const char *who, int32_t n, int32_t dim, int64_t E, int32_t 
 }
 // argument checks of the geometry gradients (geometry_grad.hip), shared with their *_host entries: 0, or 2 with the message set
 int points_grad_check(const athena_mp_graph *g, int32_t dim);
+int point_sets_grad_check(const athena_mp_graph *g, int32_t dim, bool want_queries, bool want_sources);
 int periodic_grad_check(const athena_mp_graph *g, int32_t B, int32_t n, const int32_t *offsets, const int64_t *edge_offsets,
                         float cutoff_max, bool has_dfeature, int32_t fe_cols, bool has_dvec);
 void graph_cache_clear(); // idle and live handles of athena_mp_graph_acquire (capi.hip)

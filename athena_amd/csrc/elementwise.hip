@@ -42,6 +42,12 @@ __global__ void axpy_kernel(int64_t n, float alpha, const float *__restrict__ x,
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
         y[i] = y[i] + alpha * x[i];
 }
+// y[v, :] += b: the bias of a layer whose dense step is not a GEMM with an epilogue (graph_nop without its local term)
+__global__ void add_row_bias_kernel(int64_t n, int F, const float *__restrict__ b, float *__restrict__ y)
+{
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        y[i] = y[i] + b[i % F];
+}
 
 __global__ void swish_fwd_kernel(int64_t n, float beta, const float *__restrict__ x, float *__restrict__ y)
 {
@@ -256,7 +262,14 @@ int athena_mp_axpy(int64_t n, float alpha, const float *x, float *y)
     AMP_LAUNCH_CHECK();
     return 0;
 }
-
+int athena_mp_add_row_bias(int64_t n_rows, int32_t F, const float *b, float *y)
+{
+    AMP_REQUIRE(n_rows >= 0 && F > 0 && b && (n_rows == 0 || y), "add_row_bias: bad arguments");
+    if (n_rows == 0) return 0;
+    hipLaunchKernelGGL(add_row_bias_kernel, grid_for(n_rows * F), dim3(256), 0, stream(), n_rows * F, (int)F, b, y);
+    AMP_LAUNCH_CHECK();
+    return 0;
+}
 
 /* swish_array / get_partial_swish_val, athena_diffstruc_extd_sub.f90:424-492 (reverse pass takes the INPUT) */
 int athena_mp_swish_fwd(int64_t n, float beta, const float *x, float *y)

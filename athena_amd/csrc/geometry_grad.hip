@@ -43,7 +43,7 @@ constexpr int kItemEdges = 4096;                // edges per work item of the vi
 constexpr int kVirialWaves = 4;                 // work items per 256-thread block
 constexpr int kWsTable = 17, kWsPartial = 18;   // workspace slots: the uploaded index tables, the item partials
 
-enum { kPoints = 0, kPeriodic = 1 };
+enum { kPoints = 0, kPeriodic = 1, kSetRows = 2, kSetCols = 3 };   // the last two: the plain sums of a two-set graph, + and -
 
 struct GeoEdge {                                // what the periodic term is formed from
     const float *vec, *de, *dvec;
@@ -80,7 +80,8 @@ __device__ __forceinline__ void geo_edge_term(const GeoEdge &P, int64_t e, float
     }
 }
 
-// kGroup lanes per row.  kPoints: out [n, dim] from t [E, dim].  kPeriodic: out = dcart [n, 3] (may be null) and dfrac (may be
+// kGroup lanes per row.  kPoints: out [n, dim] from t [E, dim].  kSetRows / kSetCols: the same from a CSR whose rows and columns
+// index different sets (no sign by index, no skip: every entry counts, + for kSetRows, - for kSetCols).  kPeriodic: out = dcart [n, 3] (may be null) and dfrac (may be
 // null; offsets [B + 1] and lat [B, 3, 3] on the device) from P.
 template <int MODE>
 __global__ __launch_bounds__(256) void geo_vertex_gather(int32_t n, const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col,
@@ -106,9 +107,9 @@ __global__ __launch_bounds__(256) void geo_vertex_gather(int32_t n, const int32_
         if (k0 + sub < len) {
             const int64_t k = (int64_t)beg + k0 + sub;
             const int32_t c = col[k], e = eid[k];
-            if (e >= 0 && (int64_t)c != row) {
+            if (e >= 0 && (MODE == kSetRows || MODE == kSetCols || (int64_t)c != row)) {
                 use = true;
-                if (MODE == kPoints) {
+                if (MODE != kPeriodic) {
                     const float *src = t + (int64_t)e * dim;
                     t0 = src[0];
                     if (dim > 1) t1 = src[1];
@@ -117,7 +118,7 @@ __global__ __launch_bounds__(256) void geo_vertex_gather(int32_t n, const int32_
                     float x0, x1, x2;
                     geo_edge_term(P, e, x0, x1, x2, t0, t1, t2);
                 }
-                if (row > (int64_t)c) {
+                if (MODE == kSetCols || ((MODE == kPoints || MODE == kPeriodic) && row > (int64_t)c)) {
                     t0 = -t0;
                     t1 = -t1;
                     t2 = -t2;
@@ -135,8 +136,8 @@ __global__ __launch_bounds__(256) void geo_vertex_gather(int32_t n, const int32_
             }
         }
     }
-    if (row >= n || sub >= (MODE == kPoints ? dim : 3)) return;
-    if (out) out[row * (MODE == kPoints ? dim : 3) + sub] = sub == 0 ? a0 : sub == 1 ? a1 : a2;
+    if (row >= n || sub >= (MODE != kPeriodic ? dim : 3)) return;
+    if (out) out[row * (MODE != kPeriodic ? dim : 3) + sub] = sub == 0 ? a0 : sub == 1 ? a1 : a2;
     if (MODE == kPeriodic && dfrac) {
         int32_t lo = 0, hi = B;                                     // the last structure that starts at or before this atom
         while (hi - lo > 1) {
@@ -260,7 +261,39 @@ int points_grad_check(const athena_mp_graph *g, int32_t dim)
     return 0;
 }
 
+int point_sets_grad_check(const athena_mp_graph *g, int32_t dim, bool want_queries, bool want_sources)
+{
+    AMP_REQUIRE(g != nullptr, "edge_grad_to_point_sets: null graph handle");
+    AMP_REQUIRE(dim >= 1 && dim <= 3, "edge_grad_to_point_sets: dim = %d is outside 1..3", dim);
+    AMP_REQUIRE(!(g->n_edge_cols == 0 && g->nnz > 0),
+                "edge_grad_to_point_sets: the handle has no edge columns: build it with edge ids (DeviceGraph.from_point_sets)");
+    AMP_REQUIRE(g->n_with_edge == g->nnz, "edge_grad_to_point_sets: %lld of the handle's %lld entries carry no edge id",
+                (long long)(g->nnz - g->n_with_edge), (long long)g->nnz);
+    AMP_REQUIRE(want_queries || want_sources, "edge_grad_to_point_sets: dqueries and dsources are both null: nothing to compute");
+    return 0;
+}
+
 } // namespace amp
+
+// The reverse of athena_mp_radius_pairs_bipartite, coords[e] = q_i - p_j: dqueries[i] = the sum of dcoords over row i in CSR order,
+// dsources[j] = acc - dcoords over column j in transposed-CSR order (queries ascending), acc from +0.
+extern "C" int athena_mp_edge_grad_to_point_sets(const athena_mp_graph *g, int32_t dim, const float *dcoords_dev, float *dqueries_dev,
+                                                 float *dsources_dev)
+{
+    if (int rc = amp::point_sets_grad_check(g, dim, dqueries_dev != nullptr, dsources_dev != nullptr)) return rc;
+    AMP_REQUIRE(g->n_edge_cols == 0 || dcoords_dev != nullptr, "edge_grad_to_point_sets: null dcoords");
+    const GeoEdge none = {nullptr, nullptr, nullptr, 0, 1.f};
+    if (dqueries_dev && g->n_rows > 0)
+        hipLaunchKernelGGL(geo_vertex_gather<kSetRows>, dim3((unsigned)(((int64_t)g->n_rows + kGatherRows - 1) / kGatherRows)), dim3(256), 0,
+                           amp::stream(), g->n_rows, (const int32_t *)g->rowptr, (const int32_t *)g->col, (const int32_t *)g->eid, dim,
+                           dcoords_dev, none, dqueries_dev, (float *)nullptr, (const int32_t *)nullptr, 0, (const float *)nullptr);
+    if (dsources_dev && g->n_cols > 0)
+        hipLaunchKernelGGL(geo_vertex_gather<kSetCols>, dim3((unsigned)(((int64_t)g->n_cols + kGatherRows - 1) / kGatherRows)), dim3(256), 0,
+                           amp::stream(), g->n_cols, (const int32_t *)g->t_rowptr, (const int32_t *)g->t_src, (const int32_t *)g->t_eid, dim,
+                           dcoords_dev, none, dsources_dev, (float *)nullptr, (const int32_t *)nullptr, 0, (const float *)nullptr);
+    AMP_LAUNCH_CHECK();
+    return 0;
+}
 
 extern "C" int athena_mp_edge_grad_to_points(const athena_mp_graph *g, int32_t dim, const float *dcoords_dev, float *dpoints_dev)
 {

@@ -658,6 +658,18 @@ int athena_mp_edge_grad_to_points_host(const athena_mp_graph *g, int32_t dim, co
     return staged({{dcoords, nullptr, fb(g->n_edge_cols, dim)}, {nullptr, dpoints, fb(g->n_rows, dim), true}},
                   [&](std::vector<void *> &p) { return athena_mp_edge_grad_to_points(g, dim, (float *)p[0], (float *)p[1]); });
 }
+int athena_mp_edge_grad_to_point_sets_host(const athena_mp_graph *g, int32_t dim, const float *dcoords, float *dqueries, float *dsources)
+{
+    if (int rc = point_sets_grad_check(g, dim, dqueries != nullptr, dsources != nullptr)) return rc;
+    AMP_REQUIRE(g->n_edge_cols == 0 || dcoords, "edge_grad_to_point_sets_host: null dcoords");
+    // an absent output is staged as nothing and handed on as NULL
+    auto out = [](float *h, size_t bytes) { return Stage{nullptr, h, h ? bytes : 0, true}; };
+    return staged({{dcoords, nullptr, fb(g->n_edge_cols, dim)}, out(dqueries, fb(g->n_rows, dim)), out(dsources, fb(g->n_cols, dim))},
+                  [&](std::vector<void *> &p) {
+                      return athena_mp_edge_grad_to_point_sets(g, dim, (float *)p[0], dqueries ? (float *)p[1] : nullptr,
+                                                               dsources ? (float *)p[2] : nullptr);
+                  });
+}
 int athena_mp_periodic_grad_host(const athena_mp_graph *g, int32_t B, int32_t n, const int32_t *offsets, const int64_t *edge_offsets,
                                  const float *lat, float cutoff_max, const float *vec, const float *dfeature, int32_t fe_cols,
                                  const float *dvec, float *dcart, float *dfrac, float *virial, float *dlat)

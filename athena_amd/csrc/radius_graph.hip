@@ -37,28 +37,11 @@
 
 #include "cell_grid.h"
 #include "common.h"
+#include "radius_cells.h"
 #include "radix_sort.h"
 #include "scan64.h"
 
 namespace {
-
-constexpr double kCellMargin = 1.0 / 1024.0;
-
-// ---- the predicate, term by term in fp32 (-ffp-contract=off: no fused multiply-add) --------------------------------------------
-template <int DIM> __device__ inline bool joined(const float *__restrict__ a, const float *__restrict__ b, float r2)
-{
-    const float d0 = a[0] - b[0];
-    float s = d0 * d0;
-    if (DIM > 1) {
-        const float d1 = a[1] - b[1];
-        s = s + d1 * d1;
-    }
-    if (DIM > 2) {
-        const float d2 = a[2] - b[2];
-        s = s + d2 * d2;
-    }
-    return s <= r2;
-}
 
 // One thread per slot of the cell order: the point i = perm[slot] against every point j > i of the 3^DIM cells around its own,
 // with the grid of the slot's cloud and the walk inside that cloud's cells.  FILL = false: count[i] = number of partners.
@@ -150,33 +133,6 @@ template <bool FILL, typename... A> void launch_neighbour(int dim, int32_t n, hi
     if (dim == 1) hipLaunchKernelGGL((rgb_neighbour_kernel<1, FILL>), dim3(blocks(n)), dim3(256), 0, st, n, a...);
     else if (dim == 2) hipLaunchKernelGGL((rgb_neighbour_kernel<2, FILL>), dim3(blocks(n)), dim3(256), 0, st, n, a...);
     else hipLaunchKernelGGL((rgb_neighbour_kernel<3, FILL>), dim3(blocks(n)), dim3(256), 0, st, n, a...);
-}
-
-// at most kMaxCellsAxis cells per axis and 2 n in all, every cell at least radius * (1 + kCellMargin) wide; an axis whose extent
-// is below that is one cell
-Grid make_grid(const Box &box, int dim, int32_t n, float radius)
-{
-    Grid g;
-    double extent[3] = {0, 0, 0};
-    const double h = (double)radius * (1.0 + kCellMargin);
-    for (int a = 0; a < 3; ++a) {
-        g.lo[a] = a < dim ? box.lo[a] : 0.f;
-        g.nc[a] = 1;
-        if (a < dim) {
-            extent[a] = (double)box.hi[a] - (double)box.lo[a];
-            const double cells = floor(extent[a] / h);
-            g.nc[a] = cells < 1.0 ? 1 : cells > (double)kMaxCellsAxis ? kMaxCellsAxis : (int32_t)cells;
-        }
-    }
-    const int64_t cap = std::min<int64_t>(2 * (int64_t)n, (int64_t)1 << 30);
-    while ((int64_t)g.nc[0] * g.nc[1] * g.nc[2] > cap) {
-        int a = 0;
-        for (int k = 1; k < 3; ++k)
-            if (g.nc[k] > g.nc[a]) a = k;
-        g.nc[a] = (g.nc[a] + 1) / 2;
-    }
-    for (int a = 0; a < 3; ++a) g.inv_w[a] = g.nc[a] > 1 ? (float)((double)g.nc[a] / extent[a]) : 0.f;
-    return g;
 }
 
 // how an entry speaks of itself in its messages: its name, what it calls its result, and whether it has clouds to name

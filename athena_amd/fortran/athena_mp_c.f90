@@ -52,6 +52,8 @@ module athena_mp_c
   public :: athena_mp_csr_from_edges, athena_mp_graph_export, athena_mp_graph_create_from_edges
   public :: athena_mp_graph_create_from_edges_dev, athena_mp_radius_pairs, athena_mp_radius_graph_host
   public :: athena_mp_radius_pairs_batched, athena_mp_radius_graph_batched_host
+  public :: athena_mp_radius_pairs_bipartite, athena_mp_graph_create_bipartite_dev, athena_mp_radius_graph_bipartite_host
+  public :: athena_mp_edge_grad_to_point_sets, athena_mp_edge_grad_to_point_sets_host, athena_mp_add_row_bias
   public :: athena_mp_knn_pairs_batched, athena_mp_knn_pairs, athena_mp_knn_graph_batched_host, athena_mp_knn_stats
   public :: athena_mp_periodic_pairs, athena_mp_periodic_graph_host, athena_mp_periodic_stats
   public :: athena_mp_edge_grad_to_points, athena_mp_periodic_grad
@@ -541,6 +543,48 @@ module athena_mp_c
        integer(c_int64_t), value :: capacity, coords_capacity
        integer(c_int64_t), intent(out) :: nnz, n_pairs
      end function
+     !! radius graphs between TWO point sets, a batch of clouds per call (definition: include/athena_mp.h): query_offsets and
+     !! source_offsets (n_clouds + 1) on the host, 0-based; queries (dim, n_queries) and sources (dim, n_sources) on the device ->
+     !! pairs (2, capacity) = (query, source), coords (dim, capacity) = query minus source and rowptr (n_queries + 1, 0-based) on
+     !! the device, each may be c_null_ptr (all three: n_pairs and edge_offsets only).  edge_offsets: c_loc of an
+     !! integer(c_int64_t) (n_clouds + 1) host array, or c_null_ptr
+     integer(c_int) function athena_mp_radius_pairs_bipartite(n_clouds, n_queries, query_offsets, n_sources, source_offsets, dim, &
+          queries_dev, sources_dev, radius, pairs_dev, coords_dev, capacity, rowptr_dev, edge_offsets, n_pairs) &
+          bind(C, name="athena_mp_radius_pairs_bipartite")
+       import :: c_int, c_int32_t, c_int64_t, c_float, c_ptr
+       integer(c_int32_t), value :: n_clouds, n_queries, n_sources, dim
+       integer(c_int32_t), intent(in) :: query_offsets(*), source_offsets(*)
+       type(c_ptr), value :: queries_dev, sources_dev, pairs_dev, coords_dev, rowptr_dev, edge_offsets
+       real(c_float), value :: radius
+       integer(c_int64_t), value :: capacity
+       integer(c_int64_t), intent(out) :: n_pairs
+     end function
+     !! such a pair list in HBM -> the directed rectangular handle (pair e = the one entry (row i, column j, edge id e)); adj_ia
+     !! (n_rows + 1) is always filled, adj_ja: c_loc of (2, capacity) on the host, or c_null_ptr
+     integer(c_int) function athena_mp_graph_create_bipartite_dev(n_rows, n_cols, n_pairs, pairs_dev, adj_ia, adj_ja, capacity, &
+          graph) bind(C, name="athena_mp_graph_create_bipartite_dev")
+       import :: c_int, c_int32_t, c_int64_t, c_ptr
+       integer(c_int32_t), value :: n_rows, n_cols
+       integer(c_int64_t), value :: n_pairs, capacity
+       type(c_ptr), value :: pairs_dev, adj_ja
+       integer(c_int32_t), intent(inout) :: adj_ia(*)
+       type(c_ptr), intent(out) :: graph
+     end function
+     !! the search with host arrays: queries (dim, n_queries), sources (dim, n_sources) -> adj_ia (n_queries + 1), adj_ja
+     !! (2, capacity) = (source, edge id), coords (dim, coords_capacity), edge_offsets (n_clouds + 1); adj_ja = c_null_ptr queries
+     !! n_pairs and edge_offsets
+     integer(c_int) function athena_mp_radius_graph_bipartite_host(n_clouds, n_queries, query_offsets, n_sources, source_offsets, &
+          dim, queries, sources, radius, adj_ia, adj_ja, capacity, coords, coords_capacity, edge_offsets, n_pairs) &
+          bind(C, name="athena_mp_radius_graph_bipartite_host")
+       import :: c_int, c_int32_t, c_int64_t, c_float, c_ptr
+       integer(c_int32_t), value :: n_clouds, n_queries, n_sources, dim
+       integer(c_int32_t), intent(in) :: query_offsets(*), source_offsets(*)
+       real(c_float), intent(in) :: queries(dim, *), sources(dim, *)
+       real(c_float), value :: radius
+       type(c_ptr), value :: adj_ia, adj_ja, coords, edge_offsets
+       integer(c_int64_t), value :: capacity, coords_capacity
+       integer(c_int64_t), intent(out) :: n_pairs
+     end function
      !! a batch of point clouds -> ONE block-diagonal k-nearest-neighbour pair list (definition: include/athena_mp.h): the first k
      !! others of every point in the order (squared distance, index), inside radius when it is finite (ieee +infinity: no cap);
      !! mode 0 = union, 1 = mutual.  nbr (k, n), pairs (2, capacity), coords (dim, capacity) on the device, each may be
@@ -652,6 +696,22 @@ module athena_mp_c
        integer(c_int32_t), value :: dim
        real(c_float), intent(in) :: dcoords(dim, *)
        real(c_float), intent(inout) :: dpoints(dim, *)
+     end function
+     !! the reverse of athena_mp_radius_pairs_bipartite on its rectangular handle: dcoords (dim, E) -> dqueries (dim, n_rows) = the
+     !! sum over each row, dsources (dim, n_cols) = minus the sum over each column; each output may be c_null_ptr, not both
+     integer(c_int) function athena_mp_edge_grad_to_point_sets(graph, dim, dcoords_dev, dqueries_dev, dsources_dev) &
+          bind(C, name="athena_mp_edge_grad_to_point_sets")
+       import :: c_int, c_int32_t, c_ptr
+       type(c_ptr), value :: graph, dcoords_dev, dqueries_dev, dsources_dev
+       integer(c_int32_t), value :: dim
+     end function
+     !! the same with host arrays (staged); dqueries, dsources: c_loc of the host arrays, or c_null_ptr
+     integer(c_int) function athena_mp_edge_grad_to_point_sets_host(graph, dim, dcoords, dqueries, dsources) &
+          bind(C, name="athena_mp_edge_grad_to_point_sets_host")
+       import :: c_int, c_int32_t, c_float, c_ptr
+       type(c_ptr), value :: graph, dqueries, dsources
+       integer(c_int32_t), value :: dim
+       real(c_float), intent(in) :: dcoords(dim, *)
      end function
      !! ... dfeature, dvec and the four outputs passed as c_loc of host arrays, or c_null_ptr
      integer(c_int) function athena_mp_periodic_grad_host(graph, n_structures, n_atoms, offsets, edge_offsets, lat, cutoff_max, &
@@ -882,6 +942,13 @@ module athena_mp_c
        integer(c_int64_t), value :: n
        real(c_float), value :: alpha
        type(c_ptr), value :: x_dev, y_dev
+     end function
+     !! y(:, v) = y(:, v) + b for the n_rows columns of y (f, n_rows): the bias of a layer whose dense step is no GEMM
+     integer(c_int) function athena_mp_add_row_bias(n_rows, f, b_dev, y_dev) bind(C, name="athena_mp_add_row_bias")
+       import :: c_int, c_int32_t, c_int64_t, c_ptr
+       integer(c_int64_t), value :: n_rows
+       integer(c_int32_t), value :: f
+       type(c_ptr), value :: b_dev, y_dev
      end function
      integer(c_int) function athena_mp_kipf_propagate_act_fwd(graph, F, x_dev, act, y_dev) &
           bind(C, name="athena_mp_kipf_propagate_act_fwd")

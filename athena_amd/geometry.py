@@ -10,6 +10,10 @@
     g = structures_grad(handle, lat, voff, eoff, vec, cutoff_max, dfeature=de)
     forces = -g["cart"];  g["frac"], g["virial"], g["lat"]
 
+    handle, coords, eoff = DeviceGraph.from_point_sets(queries, sources, radius)    # coords[e] = q_i - p_j
+    ... graph_nop_layer_type(local_term=False).backward(need_coord_grad=True) -> dcoords [E, d]
+    g = point_sets_grad(handle, dcoords);  g["queries"] [n_queries, d], g["sources"] [n_sources, d]
+
 There is no autograd wrapper: these are the reverse steps themselves, to be called where the chain needs them."""
 import ctypes as C
 
@@ -41,6 +45,38 @@ def points_grad(handle, dcoords, out=None):
     _capi.use_torch_stream()
     _capi.call("athena_mp_edge_grad_to_points", handle.handle, dim, C.c_void_p(dcoords.data_ptr()), C.c_void_p(out.data_ptr()))
     return out
+
+
+def point_sets_grad(handle, dcoords, want=("queries", "sources"), out=None):
+    """The reverse of DeviceGraph.from_point_sets (athena_mp_edge_grad_to_point_sets): dcoords [E, dim] float32 on the device, the
+    gradient with respect to coords[e] = q_i - p_j -> a dict of device tensors for the names in `want`: "queries" [n_queries, dim],
+    row i = the sum of dcoords over the handle's row i in CSR order; "sources" [n_sources, dim], row j = minus the sum over the
+    handle's column j, queries ascending; bit for bit the sequential sums.  out: a dict of contiguous float32 device tensors to
+    write into, by the same names."""
+    import torch
+
+    if not (isinstance(dcoords, torch.Tensor) and dcoords.is_cuda and dcoords.dtype == torch.float32 and dcoords.dim() == 2
+            and dcoords.is_contiguous()):
+        raise ValueError("dcoords must be a contiguous float32 device tensor [E, dim]")
+    E, dim = int(dcoords.shape[0]), int(dcoords.shape[1])
+    if E != handle.n_edge_cols:
+        raise ValueError(f"dcoords holds {E} rows, the handle has {handle.n_edge_cols} edge columns")
+    want = tuple(want)
+    if not want or any(w not in ("queries", "sources") for w in want):
+        raise ValueError('want must name some of ("queries", "sources")')
+    shapes = {"queries": (handle.n_rows, dim), "sources": (handle.n_cols, dim)}
+    res = {}
+    for w in want:
+        t = None if out is None else out.get(w)
+        if t is None:
+            t = torch.empty(shapes[w], dtype=torch.float32, device=dcoords.device)
+        elif not (t.is_cuda and t.dtype == torch.float32 and tuple(t.shape) == shapes[w] and t.is_contiguous()):
+            raise ValueError(f"out[{w!r}] must be a contiguous float32 device tensor {shapes[w]}")
+        res[w] = t
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    _capi.use_torch_stream()
+    _capi.call("athena_mp_edge_grad_to_point_sets", handle.handle, dim, ptr(dcoords), ptr(res.get("queries")), ptr(res.get("sources")))
+    return res
 
 
 def _host_tables(handle, lat_rows, offsets, edge_offsets, want):

@@ -573,6 +573,67 @@ class DeviceGraph:
         return self, coords, off.copy(), eoff
 
     @classmethod
+    def from_point_sets(cls, queries, sources, radius, query_offsets=None, source_offsets=None, want_adjacency=False, device=0):
+        """Two point sets -> the directed, rectangular device handle that joins every query to the sources of its cloud inside
+        the radius, without the pair list leaving HBM (athena_mp_radius_pairs_bipartite, then
+        athena_mp_graph_create_bipartite_dev): the graph graph_nop_layer_type(local_term=False) integrates over when its output
+        points are not its input points.  queries [n_queries, dim] and sources [n_sources, dim] float32, dim 1..3: numpy arrays,
+        or torch tensors already on the device; query_offsets / source_offsets [B + 1] 0-based on the host (both or neither:
+        without them the sets are one cloud), empty slices allowed; one radius for all.  The definition of the pairs (fp32, term
+        by term; no self-pair rule) is in include/athena_mp.h.  Returns (handle, coords, edge_offsets) or, with want_adjacency,
+        (..., adj_ia, adj_ja): handle.n_rows = n_queries, handle.n_cols = n_sources, one CSR entry and one edge column per pair;
+        coords is a device tensor [num_edges, dim] = q_i - p_j, rows in lexicographic order of (i, j); edge_offsets (int64) is
+        numpy [B + 1]."""
+        import torch
+
+        _capi.init(device)
+        dev = torch.device("cuda", device)
+
+        def on_device(p, what):
+            if isinstance(p, torch.Tensor):
+                t = p.to(dev, torch.float32).contiguous()
+            else:
+                t = torch.from_numpy(np.ascontiguousarray(p, dtype=np.float32)).to(dev)
+            if t.dim() != 2:
+                raise ValueError(f"{what} must be [n, dim]")
+            return t
+
+        q, s = on_device(queries, "queries"), on_device(sources, "sources")
+        if q.shape[1] != s.shape[1]:
+            raise ValueError(f"queries have {q.shape[1]} components, sources {s.shape[1]}")
+        nq, ns, dim = int(q.shape[0]), int(s.shape[0]), int(q.shape[1])
+        if (query_offsets is None) != (source_offsets is None):
+            raise ValueError("query_offsets and source_offsets must be given together")
+        qoff = np.ascontiguousarray([0, nq] if query_offsets is None else query_offsets, dtype=np.int32)
+        soff = np.ascontiguousarray([0, ns] if source_offsets is None else source_offsets, dtype=np.int32)
+        if qoff.ndim != 1 or qoff.size < 1 or soff.shape != qoff.shape:
+            raise ValueError("query_offsets and source_offsets must both be [B + 1]")
+        B = int(qoff.size - 1)
+        _capi.use_torch_stream()
+        ptr = lambda t: C.c_void_p(t.data_ptr())
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        E = C.c_int64()
+        eoff = np.empty(B + 1, np.int64)
+        head = (B, nq, vp(qoff), ns, vp(soff), dim, ptr(q), ptr(s), float(radius))
+        _capi.call("athena_mp_radius_pairs_bipartite", *head, None, None, 0, None, vp(eoff), C.byref(E))
+        pairs = torch.empty((E.value, 2), dtype=torch.int32, device=dev)       # the memory of a column-major [2, E]
+        coords = torch.empty((E.value, dim), dtype=torch.float32, device=dev)
+        _capi.call("athena_mp_radius_pairs_bipartite", *head, ptr(pairs), ptr(coords), E.value, None, vp(eoff), C.byref(E))
+        self = cls.__new__(cls)
+        ia = np.empty(nq + 1, np.int32)
+        h = C.c_void_p()
+        ja = np.empty((2, E.value), np.int32, order="F") if want_adjacency else None
+        _capi.call("athena_mp_graph_create_bipartite_dev", nq, ns, E.value, ptr(pairs), vp(ia), vp(ja) if ja is not None else None,
+                   E.value if ja is not None else 0, C.byref(h))
+        self.handle = h
+        self.n_rows, self.n_cols = nq, ns
+        self.nnz = int(E.value)
+        self.n_edge_cols = int(E.value)
+        if want_adjacency:
+            return self, coords, eoff, ia, ja
+        return self, coords, eoff
+
+    @classmethod
     def from_point_clouds_knn(cls, points, offsets, k, radius=None, mode="union", add_self_loops=False, want_adjacency=False,
                               want_neighbours=False, device=0):
         """A batch of point clouds -> one block-diagonal k-nearest-neighbour device handle without the pair list leaving HBM

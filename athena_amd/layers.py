@@ -559,8 +559,12 @@ class graph_nop_layer_type(msgpass_layer_type):
 
     def __init__(self, num_outputs, coord_dim, kernel_hidden=None, num_inputs=None, use_bias=True,
                  activation="none", kernel_initialiser=None, bias_initialiser=None, verbose=0,
-                 device="cuda:0", seed=0, keep_s=None):
+                 device="cuda:0", seed=0, keep_s=None, local_term=True):
         super().__init__(device, seed)
+        # local_term: the reference's layer, out = act(m + W x + b).  False: the integral transform alone, out = act(m + b), with
+        # params = [theta] + ([b] if use_bias) -- the form that has a meaning on a rectangular handle
+        # (DeviceGraph.from_point_sets: x [n_cols, F_in] on the sources -> out [n_rows, F_out] on the queries), where W x has none
+        self.local_term = bool(local_term)
         # keep_s: the forward pass keeps S = sum_e [h_e;1] x_j^T per vertex for the reverse pass (the reference keeps every
         # forward intermediate on its tape).  None: whenever the shape takes the kernels that do and S is at most
         # ATHENA_MP_GNO_KEEP_S_MAX_GB (default 64: BASELINE configs[3] needs 33 of the 288 GB); True / False: always / never.
@@ -587,7 +591,9 @@ class graph_nop_layer_type(msgpass_layer_type):
         theta = np.concatenate([
             _init_weights(r, H * d, d, H, self.activation), np.zeros(H, np.float32),
             _init_weights(r, F * H, H, F, self.activation), np.zeros(F, np.float32)])
-        self.params = [self._t(theta), self._t(_init_weights(r, Fo * Fi, Fi + int(self.use_bias), Fo, self.activation))]
+        self.params = [self._t(theta)]
+        if self.local_term:
+            self.params.append(self._t(_init_weights(r, Fo * Fi, Fi + int(self.use_bias), Fo, self.activation)))
         if self.use_bias:
             self.params.append(self._t(np.zeros(Fo, np.float32)))
         self.grads = [None] * len(self.params)
@@ -602,6 +608,10 @@ class graph_nop_layer_type(msgpass_layer_type):
             raise RuntimeError("graph_nop layer expects vertex and edge feature inputs")   # :725-728
         if not (x.shape == (g.n_cols, Fi) and coords.shape == (g.n_edge_cols, self.coord_dim)):
             raise ValueError('expected: x.shape == (g.n_cols, Fi) and coords.shape == (g.n_edge_cols, self.coord_dim)')
+        if self.local_term and g.n_rows != g.n_cols:
+            raise ValueError(f"graph_nop layer: the handle is rectangular ({g.n_rows} rows, {g.n_cols} columns) and the local term "
+                             "W x has no meaning when the output points are not the input points: build the layer with "
+                             "local_term=False")
         self._x, self._coords = x, coords
         self._s_valid = False
         m = None
@@ -616,8 +626,11 @@ class graph_nop_layer_type(msgpass_layer_type):
                 self.keep_s, self._s_save = False, None        # no room for S beside the model: rebuild it from now on
         if m is None:
             m = ops.gno_aggregate(g, self.params[0], coords, x, self.coord_dim, self.kernel_hidden, Fo)   # steps 1+2
-        z = ops.matmul(self.params[1], x, Fo, bias=self.params[2] if self.use_bias else None)          # steps 3+5
-        ops.axpy(1.0, m, z)                                                                            # step 4
+        if self.local_term:
+            z = ops.matmul(self.params[1], x, Fo, bias=self.params[2] if self.use_bias else None)      # steps 3+5
+            ops.axpy(1.0, m, z)                                                                        # step 4
+        else:
+            z = ops.add_row_bias(self.params[1], m) if self.use_bias else m                            # step 5 alone
         out = ops.activation(self.activation, z) if not _identity(self.activation) else z               # step 6
         self._z = z if ops.needs_input(self.activation) else None
         self.output = out
@@ -644,8 +657,9 @@ class graph_nop_layer_type(msgpass_layer_type):
         dz = ops.activation_bwd(self.activation, self.output, gup, z=self._z) if not _identity(self.activation) else gup
         if self.use_bias:
             ones = torch.ones((dz.shape[0], 1), device=self.device)
-            self.grads[2] = ops.matmul_dw(ones, dz)          # db[o] = sum_v dz[v,o]
-        self.grads[1] = ops.matmul_dw(self._x, dz)
+            self.grads[-1] = ops.matmul_dw(ones, dz)         # db[o] = sum_v dz[v,o]
+        if self.local_term:
+            self.grads[1] = ops.matmul_dw(self._x, dz)
         # the whole reverse pass of gno_aggregate from ONE G = dz . Vmat^T (athena_mp_gno_aggregate_bwd: the kernel that
         # holds a piece of G_i in LDS for the kernel MLP's gradient also emits every entry's partial of dx)
         dxa, self.grads[0], dc, _ = ops.gno_aggregate_bwd(g, self.params[0], self._coords, self._x, dz, d, H,
@@ -653,8 +667,11 @@ class graph_nop_layer_type(msgpass_layer_type):
                                                           need_dx=need_input_grad, need_dcoords=need_coord_grad)
         dx = None
         if need_input_grad:
-            dx = ops.matmul_dx(self.params[1], dz, Fi)
-            ops.axpy(1.0, dxa, dx)
+            if self.local_term:
+                dx = ops.matmul_dx(self.params[1], dz, Fi)
+                ops.axpy(1.0, dxa, dx)
+            else:
+                dx = dxa
         return (dx, dc) if need_coord_grad else dx
 
 

@@ -391,6 +391,14 @@ def axpy(alpha, x, y):
     return y
 
 
+def add_row_bias(b, y):
+    """y[v, :] += b in place (athena_mp_add_row_bias): y [n, F], b [F]"""
+    _go()
+    n, F = y.shape
+    _capi.call("athena_mp_add_row_bias", n, F, _p(_chk(b, (F,))), _p(_chk(y)))
+    return y
+
+
 # ---- Duvenaud -------------------------------------------------------------------------------------
 def duvenaud_propagate(g: DeviceGraph, x, e, out=None):
     """athena_diffstruc_extd_sub_duvenaud.f90:7-59"""

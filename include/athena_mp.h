@@ -168,6 +168,49 @@ int athena_mp_radius_graph_batched_host(int32_t n_clouds, int32_t n, const int32
                                         const float *points_host, float radius, int32_t add_self_loops, int32_t *adj_ia_out,
                                         int32_t *adj_ja_out, int64_t capacity, int64_t *nnz_out, float *coords_out,
                                         int64_t coords_capacity, int64_t *n_pairs_out, int64_t *edge_offsets_out);
+/* Radius graphs between TWO point sets on the device, a batch of clouds per call (bipartite_graph.hip): every query is joined to
+ * the sources of its cloud inside the radius -- the graph a graph neural operator integrates over when its output points are not
+ * its input points (a mesh onto a latent grid, a latent grid onto query points, coarse onto fine, sensors onto a mesh).  Every
+ * implementation gives the same arrays.
+ *   queries [n_queries, dim] and sources [n_sources, dim] fp32 row-major on the device, dim in 1..3; query_offsets and
+ *   source_offsets [n_clouds + 1] int32 on the HOST, 0-based, ascending from 0 to n_queries / n_sources: cloud b owns the queries
+ *   query_offsets[b] .. query_offsets[b+1]-1 and the sources source_offsets[b] .. source_offsets[b+1]-1; either slice may be
+ *   empty, in any cloud; one radius fp32 > 0 for all clouds.
+ *   Which pairs join: query i and source j of the same cloud are joined iff s <= fl(radius * radius), with d = q_i - p_j per
+ *   component in fp32 and s = ((d0*d0) + d1*d1) + d2*d2, every operation rounded on its own: the predicate of
+ *   athena_mp_radius_pairs, unchanged.  The two sets have separate index spaces: there is no self-pair rule, a query that
+ *   coincides with a source is joined to it, and i == j means nothing.
+ *   Numbering: pairs are numbered in lexicographic order of the global (i, j).  pairs [2, capacity] column-major, 1-based: row 1
+ *   the query, row 2 the source; coords [capacity, dim], coords[e, :] = q_i - p_j (query minus source); rowptr [n_queries + 1]
+ *   int32 on the device (may be NULL): rowptr[i] = the 0-based number of pairs whose query is below i, rowptr[n_queries] = the
+ *   number of pairs; edge_offsets [n_clouds + 1] int64 on the HOST (may be NULL): edge_offsets[b] = rowptr[query_offsets[b]].
+ * pairs_dev, coords_dev and rowptr_dev all NULL: size query (the count pass only; edge_offsets is still filled).  Each may be NULL
+ * alone.  Refused with a message: dim outside 1..3; a radius that is not finite or <= 0 or whose square is not finite in fp32;
+ * n_clouds < 0; for either offset array, named: offsets[0] != 0, a descending offset (the cloud is named, 1-based), an end that
+ * is not the set's size; a non-finite coordinate in either set (the set, cloud, component and point of the first one are named,
+ * 1-based; the queries are looked at first); pairs >= 2^31 (found by the count pass, before anything of that size is allocated);
+ * capacity < pairs.  n_queries == 0 or n_sources == 0 succeeds with no pairs.  The library stays usable after a refusal.  Two
+ * builds of the same input are byte-identical. */
+int athena_mp_radius_pairs_bipartite(int32_t n_clouds, int32_t n_queries, const int32_t *query_offsets_host, int32_t n_sources,
+                                     const int32_t *source_offsets_host, int32_t dim, const float *queries_dev,
+                                     const float *sources_dev, float radius, int32_t *pairs_dev, float *coords_dev, int64_t capacity,
+                                     int32_t *rowptr_dev, int64_t *edge_offsets_host, int64_t *n_pairs_out);
+/* Such a pair list, already in HBM -> the directed, rectangular handle: pair e is the single CSR entry (row i, column j, edge id
+ * e); no reverse entry, no self loops.  row_deg[i] is the row's length, col_deg[j] the number of entries in column j: the handle
+ * is, array for array, what athena_mp_graph_create(n_rows, n_cols, n_pairs, adj_ia, adj_ja, n_pairs, row_deg, col_deg, ...)
+ * builds from the same CSR.  adj_ia_out [n_rows + 1] (host, 1-based) is always filled; adj_ja_out [2, capacity] (host,
+ * column-major: column, edge id) only when non-null.  The list must be strictly ascending in (i, j) with 1 <= i <= n_rows and
+ * 1 <= j <= n_cols: checked on the device, and the first offending pair is named in the refusal. */
+int athena_mp_graph_create_bipartite_dev(int32_t n_rows, int32_t n_cols, int64_t n_pairs, const int32_t *pairs_dev,
+                                         int32_t *adj_ia_out, int32_t *adj_ja_out, int64_t capacity, athena_mp_graph **out);
+/* athena_mp_radius_pairs_bipartite with every array on the host, for callers that hold Fortran arrays: adj_ia [n_queries + 1]
+ * (1-based), adj_ja [2, capacity] column-major (source, edge id: one directed entry per pair), coords [coords_capacity, dim] and
+ * edge_offsets [n_clouds + 1] (may be NULL).  adj_ja_out == NULL: size query for *n_pairs_out and edge_offsets. */
+int athena_mp_radius_graph_bipartite_host(int32_t n_clouds, int32_t n_queries, const int32_t *query_offsets_host, int32_t n_sources,
+                                          const int32_t *source_offsets_host, int32_t dim, const float *queries_host,
+                                          const float *sources_host, float radius, int32_t *adj_ia_out, int32_t *adj_ja_out,
+                                          int64_t capacity, float *coords_out, int64_t coords_capacity, int64_t *edge_offsets_out,
+                                          int64_t *n_pairs_out);
 /* A batch of point clouds -> ONE block-diagonal k-nearest-neighbour graph on the device (knn_graph.hip): the neighbour cap beside
  * the radius graphs above, for clouds whose density varies by orders of magnitude.  Every implementation gives the same arrays.
  *   points [n, dim] fp32 row-major on the device, dim in 1..3; offsets [n_clouds + 1] int32 on the HOST, 0-based, as in
@@ -289,6 +332,15 @@ int athena_mp_periodic_grad(const athena_mp_graph *g, int32_t n_structures, int3
                             const int64_t *edge_offsets_host, const float *lat_dev, float cutoff_max, const float *vec_dev,
                             const float *dfeature_dev, int32_t fe_cols, const float *dvec_dev, float *dcart_dev, float *dfrac_dev,
                             float *virial_dev, float *dlat_dev);
+/* The reverse of athena_mp_radius_pairs_bipartite (coords[e] = q_i - p_j), on a handle of athena_mp_graph_create_bipartite_dev:
+ * rows and columns index different sets, so there is no sign by index and no skipped entry.  fp32, sequential sums:
+ *   dqueries [n_rows, dim]: acc = +0; for k = rowptr[i] .. rowptr[i+1]-1 in order, acc = acc + dcoords[eid[k], :].
+ *   dsources [n_cols, dim]: acc = +0; for k = t_rowptr[j] .. t_rowptr[j+1]-1 in order (queries ascending), acc = acc - dcoords[t_eid[k], :].
+ * Every output element is written.  Each output may be NULL, not both.  Refused with a message: a handle without edge columns, a
+ * handle with an entry that carries no edge id, dim outside 1..3.  The _host form takes Fortran arrays, staged through HBM. */
+int athena_mp_edge_grad_to_point_sets(const athena_mp_graph *g, int32_t dim, const float *dcoords_dev, float *dqueries_dev,
+                                      float *dsources_dev);
+int athena_mp_edge_grad_to_point_sets_host(const athena_mp_graph *g, int32_t dim, const float *dcoords, float *dqueries, float *dsources);
 /* The same two with every array on the host (a handle plus Fortran arrays), staged through HBM */
 int athena_mp_edge_grad_to_points_host(const athena_mp_graph *g, int32_t dim, const float *dcoords, float *dpoints);
 int athena_mp_periodic_grad_host(const athena_mp_graph *g, int32_t n_structures, int32_t n_atoms, const int32_t *offsets,
@@ -482,6 +534,7 @@ int athena_mp_pull_gemm(const athena_mp_graph *g, int32_t Fi, int32_t Fo, const 
 int athena_mp_activation_fwd(int32_t act, int64_t n, const float *z_dev, float *y_dev);
 int athena_mp_activation_bwd(int32_t act, int64_t n, const float *y_dev, const float *g_dev, float *dz_dev);
 int athena_mp_axpy(int64_t n, float alpha, const float *x_dev, float *y_dev); /* y += alpha x */
+int athena_mp_add_row_bias(int64_t n_rows, int32_t F, const float *b_dev, float *y_dev); /* y[v, :] += b, y [n_rows, F] row-major */
 /* dst = src on the device, one 16-byte element per thread in launch order (stream-ordered; 16-byte aligned pointers): the
  * copy form that reaches the HBM's streaming ceiling -- bench.py --full times it on 1 GiB and prints the rate beside the roofline
  * as the measured ceiling of the box it ran on (SURVEY.md 8d "report the measured stream ceiling alongside") */
