@@ -51,6 +51,7 @@
 #include "radius_cells.h"
 #include "radix_sort.h"
 #include "scan64.h"
+#include "two_sets.h"
 
 namespace {
 
@@ -149,20 +150,6 @@ __global__ __launch_bounds__(256) void bip_neighbour_kernel(int32_t nq, int32_t 
     if (!FILL) count[i] = found;
 }
 
-// rowptr [nq + 1] (int32, may be null) and edge_offsets [B + 1] from the scan; total < 2^31 is the caller's to check
-__global__ __launch_bounds__(256) void bip_rowptr_kernel(int32_t nq, int32_t B, const int32_t *__restrict__ q_offsets,
-                                                         const unsigned long long *__restrict__ offset,
-                                                         const unsigned long long *__restrict__ total, int32_t *__restrict__ rowptr,
-                                                         long long *__restrict__ edge_offsets)
-{
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (rowptr && t <= nq) rowptr[t] = (int32_t)(t < nq ? offset[t] : *total);
-    if (edge_offsets && t <= B) {
-        const int32_t v = q_offsets[t];
-        edge_offsets[t] = (long long)(v < nq ? offset[v] : *total);
-    }
-}
-
 // ---- sorted keys -> 1-based pair list [2, E] column-major and coords [E, dim] -------------------------------------------------
 __global__ __launch_bounds__(256) void bip_emit_kernel(int64_t E, int32_t B, const int32_t *__restrict__ q_offsets,
                                                        const int32_t *__restrict__ s_offsets, unsigned long long M, int dim,
@@ -188,17 +175,6 @@ template <bool FILL, typename... A> void launch_bip_neighbour(int dim, int32_t n
     if (dim == 1) hipLaunchKernelGGL((bip_neighbour_kernel<1, FILL>), dim3(blocks(nq)), dim3(256), 0, st, nq, a...);
     else if (dim == 2) hipLaunchKernelGGL((bip_neighbour_kernel<2, FILL>), dim3(blocks(nq)), dim3(256), 0, st, nq, a...);
     else hipLaunchKernelGGL((bip_neighbour_kernel<3, FILL>), dim3(blocks(nq)), dim3(256), 0, st, nq, a...);
-}
-
-// batch_offsets_check of cell_grid.h with the array named: two offset arrays enter here
-int named_offsets_check(const char *who, const char *name, const char *unit, int32_t B, const int32_t *offsets, int32_t n)
-{
-    AMP_REQUIRE(offsets != nullptr, "%s: null %s", who, name);
-    AMP_REQUIRE(offsets[0] == 0, "%s: %s(1) = %d, not 0", who, name, offsets[0]);
-    for (int32_t b = 0; b < B; ++b)
-        AMP_REQUIRE(offsets[b + 1] >= offsets[b], "%s: cloud %d: %s descend from %d to %d", who, b + 1, name, offsets[b], offsets[b + 1]);
-    AMP_REQUIRE(offsets[B] == n, "%s: %s end at %d, the batch has %d %s", who, name, offsets[B], n, unit);
-    return 0;
 }
 
 // what every entry checks before anything touches the device: 0, or 2 with the message set

@@ -5,7 +5,7 @@
 set -e
 cd "$(dirname "$0")"
 OUT=../libathena_mp.so
-SRCS="capi.hip graph_build.hip radius_graph.hip bipartite_graph.hip knn_graph.hip periodic_graph.hip geometry_grad.hip batch_select.hip agg.hip banded_fused.hip gemm.hip gemm_tiled.hip fused.hip fused_dw.hip elementwise.hip duvenaud.hip bucket_plan.hip duv_mfma.hip readout.hip gno.hip gno64.hip train.hip host.hip comm.hip"
+SRCS="capi.hip graph_build.hip radius_graph.hip bipartite_graph.hip knn_graph.hip knn_bipartite.hip periodic_graph.hip geometry_grad.hip batch_select.hip agg.hip banded_fused.hip gemm.hip gemm_tiled.hip fused.hip fused_dw.hip elementwise.hip duvenaud.hip bucket_plan.hip duv_mfma.hip readout.hip gno.hip gno64.hip train.hip host.hip comm.hip"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-function"
 mkdir -p ../../build/obj
 objs=""
@@ -14,7 +14,7 @@ for s in $SRCS; do
   [ -f "$s" ] || continue
   o=../../build/obj/${s%.hip}.o
   objs="$objs $o"
-  if [ ! -f "$o" ] || [ "$s" -nt "$o" ] || [ common.h -nt "$o" ] || [ transport.h -nt "$o" ] || [ radix_sort.h -nt "$o" ] || [ scan64.h -nt "$o" ] || [ cell_grid.h -nt "$o" ] || [ radius_cells.h -nt "$o" ] || [ cell_start.h -nt "$o" ] || [ ../../include/athena_mp.h -nt "$o" ]; then
+  if [ ! -f "$o" ] || [ "$s" -nt "$o" ] || [ common.h -nt "$o" ] || [ transport.h -nt "$o" ] || [ radix_sort.h -nt "$o" ] || [ scan64.h -nt "$o" ] || [ cell_grid.h -nt "$o" ] || [ radius_cells.h -nt "$o" ] || [ knn_cells.h -nt "$o" ] || [ two_sets.h -nt "$o" ] || [ cell_start.h -nt "$o" ] || [ ../../include/athena_mp.h -nt "$o" ]; then
     /opt/rocm/bin/hipcc $FLAGS -c "$s" -o "$o" &
     pids="$pids $!"
   fi

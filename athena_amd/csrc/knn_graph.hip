@@ -64,67 +64,11 @@
 
 #include "cell_grid.h"
 #include "common.h"
+#include "knn_cells.h"
 #include "radix_sort.h"
 #include "scan64.h"
 
 namespace {
-
-constexpr double kGridPoints = 2.0;          // points per cell the grid aims for -- not measured yet
-constexpr float kMargin = 1.0f / 1024.0f;    // 2^-10: the header's bound on what the computed cell coordinates can hide
-constexpr float kShrink = 1.0f - 0x1p-20f;   // covers the roundings of s and of the bound itself (header)
-constexpr unsigned long long kNoKey = ~0ull;
-constexpr int kQueryWaves = 4;               // query points per 256-thread block
-
-struct WLow {
-    float w[3];                              // 1 / inv_w rounded down, per axis (unused where nc = 1)
-};
-
-// the squared distance of the definition, term by term in fp32 (-ffp-contract=off: no fused multiply-add)
-template <int DIM> __device__ inline float sq_dist(const float *p, const float *q)
-{
-    const float d0 = p[0] - q[0];
-    float s = d0 * d0;
-    if (DIM > 1) {
-        const float d1 = p[1] - q[1];
-        s = s + d1 * d1;
-    }
-    if (DIM > 2) {
-        const float d2 = p[2] - q[2];
-        s = s + d2 * d2;
-    }
-    return s;
-}
-
-__device__ inline unsigned long long key_min(unsigned long long a, unsigned long long b) { return a < b ? a : b; }
-__device__ inline unsigned long long key_max(unsigned long long a, unsigned long long b) { return a < b ? b : a; }
-
-// the 64 keys of a wave, one per lane, ascending by lane
-__device__ inline unsigned long long wave_sort(unsigned long long c, int lane)
-{
-#pragma unroll
-    for (int size = 2; size <= 64; size <<= 1) {
-        const bool up = (lane & size) == 0;                  // the last round (size 64) ascends in every lane
-#pragma unroll
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            const unsigned long long o = __shfl_xor(c, stride, 64);
-            const bool low = (lane & stride) == 0;
-            c = low == up ? key_min(c, o) : key_max(c, o);
-        }
-    }
-    return c;
-}
-
-// list and step both ascending by lane: the 64 smallest keys of the two, ascending by lane
-__device__ inline unsigned long long wave_merge(unsigned long long list, unsigned long long step, int lane)
-{
-    unsigned long long c = key_min(list, __shfl(step, 63 - lane, 64));     // bitonic, and it holds the 64 smallest
-#pragma unroll
-    for (int stride = 32; stride > 0; stride >>= 1) {
-        const unsigned long long o = __shfl_xor(c, stride, 64);
-        c = (lane & stride) == 0 ? key_min(c, o) : key_max(c, o);
-    }
-    return c;
-}
 
 // One wave per slot of the cell order: the point i = perm[slot] against the cells of its cloud, shell by shell (header).
 // nbr[i, 0..k-1] = N_k(i) as 1-based global ids in key order, padded with 0.  stat[0][slot] = candidates read, stat[1][slot] =
@@ -222,33 +166,6 @@ __global__ __launch_bounds__(64 * kQueryWaves) void knn_search_kernel(int32_t n,
     }
 }
 
-// stat [3][n] -> out[block] = {sum, sum, max}: block partials, folded on the host in block order
-constexpr int kStatBlocks = 256;
-__global__ __launch_bounds__(256) void knn_stat_kernel(int32_t n, const uint32_t *__restrict__ stat, unsigned long long *__restrict__ out)
-{
-    __shared__ unsigned long long part[3][256];
-    unsigned long long c = 0, v = 0, r = 0;
-    for (int64_t s = (int64_t)blockIdx.x * 256 + threadIdx.x; s < n; s += (int64_t)gridDim.x * 256) {
-        c += stat[s];
-        v += stat[(int64_t)n + s];
-        const unsigned long long x = stat[2 * (int64_t)n + s];
-        r = x > r ? x : r;
-    }
-    part[0][threadIdx.x] = c;
-    part[1][threadIdx.x] = v;
-    part[2][threadIdx.x] = r;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) {
-            part[0][threadIdx.x] += part[0][threadIdx.x + s];
-            part[1][threadIdx.x] += part[1][threadIdx.x + s];
-            part[2][threadIdx.x] = key_max(part[2][threadIdx.x], part[2][threadIdx.x + s]);
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x < 3) out[3 * blockIdx.x + threadIdx.x] = part[threadIdx.x][0];
-}
-
 // ---- symmetrise ---------------------------------------------------------------------------------------------------------------
 // entry e = (i, t) of nbr -> min * n + max, padding -> n * n (above every pair)
 __global__ __launch_bounds__(256) void knn_pair_key_kernel(int64_t T, int32_t n, int k, const int32_t *__restrict__ nbr,
@@ -311,61 +228,6 @@ __global__ __launch_bounds__(256) void knn_edge_offsets_kernel(int32_t B, int32_
 
 using amp::Scratch;
 
-float round_down(double v)
-{
-    float f = (float)v;
-    if ((double)f > v) f = nextafterf(f, 0.f);
-    return f;
-}
-
-// About kGridPoints points per cell, at most kMaxCellsAxis cells per axis and 2 m in all.  An axis of zero extent is one cell; so
-// is one whose inv_w would not be a normal fp32 number with the relative accuracy the header's proof uses.
-Grid make_knn_grid(const Box &box, int dim, int32_t m, WLow *wl)
-{
-    Grid g;
-    double extent[3] = {0, 0, 0}, volume = 1.0;
-    int active = 0;
-    for (int a = 0; a < 3; ++a) {
-        g.lo[a] = a < dim ? box.lo[a] : 0.f;
-        g.nc[a] = 1;
-        g.inv_w[a] = 0.f;
-        wl->w[a] = 0.f;
-        if (a < dim) extent[a] = (double)box.hi[a] - (double)box.lo[a];
-        if (extent[a] > 0.0 && extent[a] < 1e37) {
-            volume *= extent[a];
-            ++active;
-        } else {
-            extent[a] = 0.0;
-        }
-    }
-    if (active == 0) return g;
-    const double want = std::max(1.0, (double)m / kGridPoints);
-    const double w = pow(volume / want, 1.0 / active);
-    for (int a = 0; a < 3; ++a) {
-        if (extent[a] == 0.0) continue;
-        const double cells = floor(extent[a] / w);
-        g.nc[a] = !(cells >= 1.0) ? 1 : cells > (double)kMaxCellsAxis ? kMaxCellsAxis : (int32_t)cells;
-    }
-    const int64_t cap = std::min<int64_t>(2 * (int64_t)m, (int64_t)1 << 30);
-    while ((int64_t)g.nc[0] * g.nc[1] * g.nc[2] > cap) {
-        int a = 0;
-        for (int c = 1; c < 3; ++c)
-            if (g.nc[c] > g.nc[a]) a = c;
-        g.nc[a] = (g.nc[a] + 1) / 2;
-    }
-    for (int a = 0; a < 3; ++a) {
-        if (g.nc[a] <= 1) continue;
-        const float inv_w = (float)((double)g.nc[a] / extent[a]);
-        if (!(inv_w >= 1e-30f && inv_w <= 1e30f)) {
-            g.nc[a] = 1;
-            continue;
-        }
-        g.inv_w[a] = inv_w;
-        wl->w[a] = round_down((1.0 / (double)inv_w) * (1.0 - 0x1p-30));
-    }
-    return g;
-}
-
 template <typename... A> void launch_search(int dim, int32_t n, hipStream_t st, A... a)
 {
     const dim3 grid((unsigned)(((int64_t)n + kQueryWaves - 1) / kQueryWaves)), block(64 * kQueryWaves);
@@ -374,7 +236,6 @@ template <typename... A> void launch_search(int dim, int32_t n, hipStream_t st, 
     else hipLaunchKernelGGL(knn_search_kernel<3>, grid, block, 0, st, n, a...);
 }
 
-int64_t g_stats[4] = {0, 0, 0, 0};       // athena_mp_knn_stats: of the last call
 
 int knn_arguments_check(const char *who, int32_t B, const int32_t *offsets, int32_t dim, int32_t k, float radius, int32_t mode)
 {
@@ -389,6 +250,8 @@ int knn_arguments_check(const char *who, int32_t B, const int32_t *offsets, int3
 
 namespace amp {
 
+int64_t g_knn_stats[4] = {0, 0, 0, 0};       // athena_mp_knn_stats: of the last call, of either builder
+
 // nbr_dev, pairs_dev and coords_dev all null: size query (edge_offsets_out is filled either way).  Everything on the library's
 // stream; synchronised on return.
 int knn_pairs_batched_core(int32_t B, int32_t n, const int32_t *offsets, int32_t dim, const float *points_dev, int32_t k, float radius,
@@ -398,7 +261,7 @@ int knn_pairs_batched_core(int32_t B, int32_t n, const int32_t *offsets, int32_t
     static const char who[] = "knn_pairs_batched";
     AMP_REQUIRE(n_pairs_out != nullptr, "knn_pairs_batched: null n_pairs_out");
     *n_pairs_out = 0;
-    std::fill(g_stats, g_stats + 4, (int64_t)0);
+    std::fill(g_knn_stats, g_knn_stats + 4, (int64_t)0);
     if (int rc = knn_arguments_check(who, B, offsets, dim, k, radius, mode)) return rc;
     AMP_REQUIRE(offsets[B] == n, "knn_pairs_batched: offsets end at %d, the batch has %d points", offsets[B], n);
     AMP_REQUIRE(n == 0 || points_dev != nullptr, "knn_pairs_batched: null points");
@@ -463,12 +326,7 @@ int knn_pairs_batched_core(int32_t B, int32_t n, const int32_t *offsets, int32_t
     if (edge_offsets_out)
         AMP_HIP(hipMemcpyAsync(edge_offsets_out, d_edge_off, sizeof(int64_t) * ((size_t)B + 1), hipMemcpyDeviceToHost, st));
     AMP_HIP(hipStreamSynchronize(st));
-    g_stats[0] = n;
-    for (int s = 0; s < stat_blocks; ++s) {
-        g_stats[1] += (int64_t)stat_part[3 * s];
-        g_stats[2] += (int64_t)stat_part[3 * s + 1];
-        g_stats[3] = std::max(g_stats[3], (int64_t)stat_part[3 * s + 2]);
-    }
+    knn_stats_fold(n, stat_blocks, stat_part);
     *n_pairs_out = (int64_t)total;
     if (!fill) return 0;
     AMP_REQUIRE(capacity >= (int64_t)total, "knn_pairs_batched: the output buffers hold %lld pairs, the graph has %lld", (long long)capacity,
@@ -503,7 +361,7 @@ extern "C" int athena_mp_knn_pairs(int32_t n, int32_t dim, const float *points_d
 extern "C" int athena_mp_knn_stats(int64_t out[4])
 {
     AMP_REQUIRE(out != nullptr, "knn_stats: null output");
-    std::copy(g_stats, g_stats + 4, out);
+    std::copy(amp::g_knn_stats, amp::g_knn_stats + 4, out);
     return 0;
 }
 

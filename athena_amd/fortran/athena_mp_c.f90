@@ -55,6 +55,7 @@ module athena_mp_c
   public :: athena_mp_radius_pairs_bipartite, athena_mp_graph_create_bipartite_dev, athena_mp_radius_graph_bipartite_host
   public :: athena_mp_edge_grad_to_point_sets, athena_mp_edge_grad_to_point_sets_host, athena_mp_add_row_bias
   public :: athena_mp_knn_pairs_batched, athena_mp_knn_pairs, athena_mp_knn_graph_batched_host, athena_mp_knn_stats
+  public :: athena_mp_knn_pairs_bipartite, athena_mp_knn_graph_bipartite_host
   public :: athena_mp_periodic_pairs, athena_mp_periodic_graph_host, athena_mp_periodic_stats
   public :: athena_mp_edge_grad_to_points, athena_mp_periodic_grad
   public :: athena_mp_edge_grad_to_points_host, athena_mp_periodic_grad_host
@@ -627,6 +628,37 @@ module athena_mp_c
      integer(c_int) function athena_mp_knn_stats(out) bind(C, name="athena_mp_knn_stats")
        import :: c_int, c_int64_t
        integer(c_int64_t), intent(out) :: out(4)
+     end function
+     !! k-nearest-neighbour graphs between TWO point sets, a batch of clouds per call (definition: include/athena_mp.h): every
+     !! query joined to the first k sources of its cloud in the order (squared distance, index), inside radius when it is finite
+     !! (ieee +infinity: no cap).  Inputs as athena_mp_radius_pairs_bipartite; nbr (k, n_queries) and sqdist (k, n_queries) in key
+     !! order, pairs (2, capacity) = (query, source), coords (dim, capacity) and rowptr (n_queries + 1, 0-based) on the device,
+     !! each may be c_null_ptr (all five: n_pairs and edge_offsets only); capacity = n_queries * k always suffices
+     integer(c_int) function athena_mp_knn_pairs_bipartite(n_clouds, n_queries, query_offsets, n_sources, source_offsets, dim, &
+          queries_dev, sources_dev, k, radius, nbr_dev, sqdist_dev, pairs_dev, coords_dev, capacity, rowptr_dev, edge_offsets, &
+          n_pairs) bind(C, name="athena_mp_knn_pairs_bipartite")
+       import :: c_int, c_int32_t, c_int64_t, c_float, c_ptr
+       integer(c_int32_t), value :: n_clouds, n_queries, n_sources, dim, k
+       integer(c_int32_t), intent(in) :: query_offsets(*), source_offsets(*)
+       type(c_ptr), value :: queries_dev, sources_dev, nbr_dev, sqdist_dev, pairs_dev, coords_dev, rowptr_dev, edge_offsets
+       real(c_float), value :: radius
+       integer(c_int64_t), value :: capacity
+       integer(c_int64_t), intent(out) :: n_pairs
+     end function
+     !! the same with host arrays: queries (dim, n_queries), sources (dim, n_sources) -> adj_ia (n_queries + 1), adj_ja
+     !! (2, capacity) = (source, edge id), coords (dim, coords_capacity), nbr and sqdist (k, n_queries; c_null_ptr: not wanted),
+     !! edge_offsets (n_clouds + 1); adj_ja = c_null_ptr queries n_pairs and edge_offsets
+     integer(c_int) function athena_mp_knn_graph_bipartite_host(n_clouds, n_queries, query_offsets, n_sources, source_offsets, dim, &
+          queries, sources, k, radius, adj_ia, adj_ja, capacity, coords, coords_capacity, nbr, sqdist, edge_offsets, n_pairs) &
+          bind(C, name="athena_mp_knn_graph_bipartite_host")
+       import :: c_int, c_int32_t, c_int64_t, c_float, c_ptr
+       integer(c_int32_t), value :: n_clouds, n_queries, n_sources, dim, k
+       integer(c_int32_t), intent(in) :: query_offsets(*), source_offsets(*)
+       real(c_float), intent(in) :: queries(dim, *), sources(dim, *)
+       real(c_float), value :: radius
+       type(c_ptr), value :: adj_ia, adj_ja, coords, nbr, sqdist, edge_offsets
+       integer(c_int64_t), value :: capacity, coords_capacity
+       integer(c_int64_t), intent(out) :: n_pairs
      end function
      !! periodic structures -> pair list and edge geometry on the device, a batch per call (replaces get_graph_from_basis;
      !! definition: include/athena_mp.h).  offsets (n_structures + 1) and pbc (3) on the host; frac (3, n_atoms) and

@@ -29,6 +29,36 @@ def _knn_mode(mode):
     return {"union": 0, "mutual": 1}.get(mode, mode)
 
 
+def _two_sets_on_device(queries, sources, query_offsets, source_offsets, device):
+    """the inputs of the two-set builders as the C ABI takes them: (device, queries, sources) float32 [n, dim] on the device and
+    query_offsets / source_offsets [B + 1] int32 on the host (both None: one cloud); the torch stream is the library's"""
+    import torch
+
+    _capi.init(device)
+    dev = torch.device("cuda", device)
+
+    def on_device(p, what):
+        if isinstance(p, torch.Tensor):
+            t = p.to(dev, torch.float32).contiguous()
+        else:
+            t = torch.from_numpy(np.ascontiguousarray(p, dtype=np.float32)).to(dev)
+        if t.dim() != 2:
+            raise ValueError(f"{what} must be [n, dim]")
+        return t
+
+    q, s = on_device(queries, "queries"), on_device(sources, "sources")
+    if q.shape[1] != s.shape[1]:
+        raise ValueError(f"queries have {q.shape[1]} components, sources {s.shape[1]}")
+    if (query_offsets is None) != (source_offsets is None):
+        raise ValueError("query_offsets and source_offsets must be given together")
+    qoff = np.ascontiguousarray([0, q.shape[0]] if query_offsets is None else query_offsets, dtype=np.int32)
+    soff = np.ascontiguousarray([0, s.shape[0]] if source_offsets is None else source_offsets, dtype=np.int32)
+    if qoff.ndim != 1 or qoff.size < 1 or soff.shape != qoff.shape:
+        raise ValueError("query_offsets and source_offsets must both be [B + 1]")
+    _capi.use_torch_stream()
+    return dev, q, s, qoff, soff
+
+
 def _structure_arrays(frac, lat, offsets, pbc):
     """the inputs of the periodic builders as the C ABI takes them: frac [n, 3] / lat [B, 3, 3] float32, offsets [B + 1] and
     pbc [3] int32 on the host"""
@@ -586,30 +616,8 @@ class DeviceGraph:
         numpy [B + 1]."""
         import torch
 
-        _capi.init(device)
-        dev = torch.device("cuda", device)
-
-        def on_device(p, what):
-            if isinstance(p, torch.Tensor):
-                t = p.to(dev, torch.float32).contiguous()
-            else:
-                t = torch.from_numpy(np.ascontiguousarray(p, dtype=np.float32)).to(dev)
-            if t.dim() != 2:
-                raise ValueError(f"{what} must be [n, dim]")
-            return t
-
-        q, s = on_device(queries, "queries"), on_device(sources, "sources")
-        if q.shape[1] != s.shape[1]:
-            raise ValueError(f"queries have {q.shape[1]} components, sources {s.shape[1]}")
-        nq, ns, dim = int(q.shape[0]), int(s.shape[0]), int(q.shape[1])
-        if (query_offsets is None) != (source_offsets is None):
-            raise ValueError("query_offsets and source_offsets must be given together")
-        qoff = np.ascontiguousarray([0, nq] if query_offsets is None else query_offsets, dtype=np.int32)
-        soff = np.ascontiguousarray([0, ns] if source_offsets is None else source_offsets, dtype=np.int32)
-        if qoff.ndim != 1 or qoff.size < 1 or soff.shape != qoff.shape:
-            raise ValueError("query_offsets and source_offsets must both be [B + 1]")
-        B = int(qoff.size - 1)
-        _capi.use_torch_stream()
+        dev, q, s, qoff, soff = _two_sets_on_device(queries, sources, query_offsets, source_offsets, device)
+        nq, ns, dim, B = int(q.shape[0]), int(s.shape[0]), int(q.shape[1]), int(qoff.size - 1)
         ptr = lambda t: C.c_void_p(t.data_ptr())
         vp = lambda a: a.ctypes.data_as(C.c_void_p)
         E = C.c_int64()
@@ -632,6 +640,53 @@ class DeviceGraph:
         if want_adjacency:
             return self, coords, eoff, ia, ja
         return self, coords, eoff
+
+    @classmethod
+    def from_point_sets_knn(cls, queries, sources, k, radius=None, query_offsets=None, source_offsets=None, want_adjacency=False,
+                            want_neighbours=False, device=0):
+        """Two point sets -> the directed, rectangular device handle that joins every query to the first k sources of its cloud
+        in the order (fp32 squared distance, source index) -- inside radius when one is given --, without the pair list leaving
+        HBM (athena_mp_knn_pairs_bipartite, then athena_mp_graph_create_bipartite_dev): from_point_sets for queries that may lie
+        where the sources are sparse or dense, or outside them altogether.  Arguments as in from_point_sets; 1 <= k <= 64; the
+        definition is in include/athena_mp.h.  One search into buffers of n_queries * k pairs, narrowed afterwards.  Returns
+        what from_point_sets returns -- (handle, coords, edge_offsets) or, with want_adjacency, (..., adj_ia, adj_ja) -- and,
+        with want_neighbours, nbr and sqdist last: device tensors [n_queries, k], row i = the chosen sources of query i as
+        1-based global ids in key order padded with 0 (int32), and their squared distances padded with +inf (float32).  Without
+        a cap a query far outside its sources walks their whole grid: give a radius where queries may lie far away."""
+        import torch
+
+        dev, q, s, qoff, soff = _two_sets_on_device(queries, sources, query_offsets, source_offsets, device)
+        nq, ns, dim, B = int(q.shape[0]), int(s.shape[0]), int(q.shape[1]), int(qoff.size - 1)
+        k = int(k)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        E = C.c_int64()
+        eoff = np.empty(B + 1, np.int64)
+        kk = max(min(k, 64), 1)                  # a k outside 1..64 is the library's to refuse
+        cap = nq * kk
+        pairs = torch.empty((cap, 2), dtype=torch.int32, device=dev)           # the memory of a column-major [2, cap]
+        coords = torch.empty((cap, dim), dtype=torch.float32, device=dev)
+        nbr = torch.empty((nq, kk), dtype=torch.int32, device=dev) if want_neighbours else None
+        sqdist = torch.empty((nq, kk), dtype=torch.float32, device=dev) if want_neighbours else None
+        _capi.call("athena_mp_knn_pairs_bipartite", B, nq, vp(qoff), ns, vp(soff), dim, ptr(q), ptr(s), k, _knn_radius(radius), ptr(nbr),
+                   ptr(sqdist), ptr(pairs), ptr(coords), cap, None, vp(eoff), C.byref(E))
+        pairs, coords = pairs[:E.value].clone(), coords[:E.value].clone()      # narrowed: the n_queries * k buffers go back
+        self = cls.__new__(cls)
+        ia = np.empty(nq + 1, np.int32)
+        h = C.c_void_p()
+        ja = np.empty((2, E.value), np.int32, order="F") if want_adjacency else None
+        _capi.call("athena_mp_graph_create_bipartite_dev", nq, ns, E.value, ptr(pairs), vp(ia), vp(ja) if ja is not None else None,
+                   E.value if ja is not None else 0, C.byref(h))
+        self.handle = h
+        self.n_rows, self.n_cols = nq, ns
+        self.nnz = int(E.value)
+        self.n_edge_cols = int(E.value)
+        out = (self, coords, eoff)
+        if want_adjacency:
+            out += (ia, ja)
+        if want_neighbours:
+            out += (nbr, sqdist)
+        return out
 
     @classmethod
     def from_point_clouds_knn(cls, points, offsets, k, radius=None, mode="union", add_self_loops=False, want_adjacency=False,

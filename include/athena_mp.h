@@ -211,6 +211,46 @@ int athena_mp_radius_graph_bipartite_host(int32_t n_clouds, int32_t n_queries, c
                                           const float *sources_host, float radius, int32_t *adj_ia_out, int32_t *adj_ja_out,
                                           int64_t capacity, float *coords_out, int64_t coords_capacity, int64_t *edge_offsets_out,
                                           int64_t *n_pairs_out);
+/* k-nearest-neighbour graphs between TWO point sets on the device, a batch of clouds per call (knn_bipartite.hip): every query is
+ * joined to the k nearest sources of its cloud -- the rectangular graph of a graph neural operator whose queries may lie where the
+ * sources are sparse (a fixed radius finds nothing there) or dense (a fixed radius makes a hub), of PointNet++ feature propagation
+ * and of k-nearest-neighbour interpolation.  Every implementation gives the same arrays.
+ *   Inputs: those of athena_mp_radius_pairs_bipartite -- queries [n_queries, dim], sources [n_sources, dim] fp32 on the device, dim
+ *   in 1..3, query_offsets / source_offsets [n_clouds + 1] on the HOST, either slice of any cloud may be empty -- and 1 <= k <= 64
+ *   and a radius, +infinity meaning no cap.
+ *   Distance: s(i, j) from d = q_i - p_j per component, s = ((d0*d0) + d1*d1) + d2*d2, every operation rounded to fp32 on its own.
+ *   Candidates of query i: ALL sources of its cloud.  There is no self rule (separate index spaces): a query on top of a source is
+ *   joined to it at s = 0.  With a finite radius only candidates with s <= fl(radius * radius) count.  An s that overflows is +inf;
+ *   without a cap it is still a candidate and orders last.
+ *   Order: by the key (s, j), ties to the smaller source index; N_k(i) is the first min(k, candidates).
+ *   Directed outputs: nbr [n_queries, k] int32 = N_k(i) as 1-based global source ids in KEY order, padded with 0; sqdist
+ *   [n_queries, k] fp32 = the s of each entry, padded with +inf.
+ *   Graph outputs, with the conventions of athena_mp_radius_pairs_bipartite: one pair per (i, j in N_k(i)), numbered in
+ *   lexicographic order of the global (i, j) -- inside a row the sources ascend by INDEX, not by key; pairs [2, capacity] 1-based,
+ *   query first; coords[e, :] = q_i - p_j; rowptr [n_queries + 1] int32 on the device; edge_offsets [n_clouds + 1] int64 on the
+ *   HOST, edge_offsets[b] = rowptr[query_offsets[b]].  athena_mp_graph_create_bipartite_dev and
+ *   athena_mp_edge_grad_to_point_sets take the result as it is.
+ * Each of the five device outputs may be NULL alone; all NULL is a size query that still fills edge_offsets (without a cap a row's
+ * length is min(k, sources of the cloud): no search).  capacity = n_queries * k always suffices.  Refused with a message: dim
+ * outside 1..3; k outside 1..64; a radius that is NaN or <= 0; the offset errors of athena_mp_radius_pairs_bipartite, in its
+ * wording; a non-finite coordinate in either set (set, cloud, component and point named, 1-based; the queries first);
+ * n_queries * k >= 2^31; capacity < pairs.  n_queries == 0 or n_sources == 0 succeeds with no pairs.  The library stays usable after
+ * a refusal.  Two builds of the same input are byte-identical.  athena_mp_knn_stats reports this search as well.  Cost: without a
+ * cap a query d cells outside the box of its cloud's sources walks about d shells of the grid, and one far away reads all of it --
+ * correct and slow; with a cap the search ends after a few shells wherever the query lies. */
+int athena_mp_knn_pairs_bipartite(int32_t n_clouds, int32_t n_queries, const int32_t *query_offsets_host, int32_t n_sources,
+                                  const int32_t *source_offsets_host, int32_t dim, const float *queries_dev, const float *sources_dev,
+                                  int32_t k, float radius, int32_t *nbr_dev, float *sqdist_dev, int32_t *pairs_dev, float *coords_dev,
+                                  int64_t capacity, int32_t *rowptr_dev, int64_t *edge_offsets_host, int64_t *n_pairs_out);
+/* The same with every array on the host, for callers that hold Fortran arrays; it follows athena_mp_radius_graph_bipartite_host:
+ * adj_ia [n_queries + 1] (1-based), adj_ja [2, capacity] column-major (source, edge id), coords [coords_capacity, dim],
+ * edge_offsets [n_clouds + 1] (may be NULL), and nbr / sqdist [n_queries, k] (each may be NULL).  adj_ja_out == NULL: size query
+ * for *n_pairs_out and edge_offsets. */
+int athena_mp_knn_graph_bipartite_host(int32_t n_clouds, int32_t n_queries, const int32_t *query_offsets_host, int32_t n_sources,
+                                       const int32_t *source_offsets_host, int32_t dim, const float *queries_host,
+                                       const float *sources_host, int32_t k, float radius, int32_t *adj_ia_out, int32_t *adj_ja_out,
+                                       int64_t capacity, float *coords_out, int64_t coords_capacity, int32_t *nbr_out, float *sqdist_out,
+                                       int64_t *edge_offsets_out, int64_t *n_pairs_out);
 /* A batch of point clouds -> ONE block-diagonal k-nearest-neighbour graph on the device (knn_graph.hip): the neighbour cap beside
  * the radius graphs above, for clouds whose density varies by orders of magnitude.  Every implementation gives the same arrays.
  *   points [n, dim] fp32 row-major on the device, dim in 1..3; offsets [n_clouds + 1] int32 on the HOST, 0-based, as in
@@ -248,7 +288,7 @@ int athena_mp_knn_graph_batched_host(int32_t n_clouds, int32_t n, const int32_t 
                                      int32_t k, float radius, int32_t mode, int32_t add_self_loops, int32_t *adj_ia_out,
                                      int32_t *adj_ja_out, int64_t capacity, int64_t *nnz_out, float *coords_out,
                                      int64_t coords_capacity, int64_t *n_pairs_out, int64_t *edge_offsets_out);
-/* What the search of the last k-nearest-neighbour call did: out[0] = query points, out[1] = candidates examined (distances
+/* What the search of the last k-nearest-neighbour call (one set or two) did: out[0] = query points, out[1] = candidates examined (distances
  * evaluated), out[2] = grid cells visited, out[3] = the largest shell (Chebyshev cell distance) any query reached. */
 int athena_mp_knn_stats(int64_t out[4]);
 /* Periodic structures -> neighbour graphs on the device, a batch per call (periodic_graph.hip).  It replaces get_graph_from_basis
