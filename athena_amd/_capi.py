@@ -54,6 +54,9 @@ _PROTOS = {
     "athena_mp_knn_pairs_bipartite": [_i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _f32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp],
     "athena_mp_knn_graph_bipartite_host": [_i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _f32, _vp, _vp, _i64, _vp, _i64, _vp, _vp,
                                            _vp, _vp],
+    "athena_mp_farthest_points": [_i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
+    "athena_mp_farthest_points_host": [_i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
+    "athena_mp_fps_stats": [_vp],
     "athena_mp_periodic_pairs": [_i32, _i32, _vp, _vp, _vp, _vp, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp],
     "athena_mp_periodic_graph_host": [_i32, _i32, _vp, _vp, _vp, _vp, _f32, _f32, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp,
                                       _vp],

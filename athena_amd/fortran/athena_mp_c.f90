@@ -56,6 +56,7 @@ module athena_mp_c
   public :: athena_mp_edge_grad_to_point_sets, athena_mp_edge_grad_to_point_sets_host, athena_mp_add_row_bias
   public :: athena_mp_knn_pairs_batched, athena_mp_knn_pairs, athena_mp_knn_graph_batched_host, athena_mp_knn_stats
   public :: athena_mp_knn_pairs_bipartite, athena_mp_knn_graph_bipartite_host
+  public :: athena_mp_farthest_points, athena_mp_farthest_points_host, athena_mp_fps_stats
   public :: athena_mp_periodic_pairs, athena_mp_periodic_graph_host, athena_mp_periodic_stats
   public :: athena_mp_edge_grad_to_points, athena_mp_periodic_grad
   public :: athena_mp_edge_grad_to_points_host, athena_mp_periodic_grad_host
@@ -659,6 +660,33 @@ module athena_mp_c
        type(c_ptr), value :: adj_ia, adj_ja, coords, nbr, sqdist, edge_offsets
        integer(c_int64_t), value :: capacity, coords_capacity
        integer(c_int64_t), intent(out) :: n_pairs
+     end function
+     !! farthest-point sampling of a batch of clouds (definition: include/athena_mp.h): cloud b gets sample_offsets(b+1) -
+     !! sample_offsets(b) of its own points, the first one start(b) (1-based global; 0: the cloud's first point), each next one
+     !! the point not yet chosen that is farthest from those chosen, ties to the smaller index.  offsets, sample_offsets
+     !! (n_clouds + 1) and start (c_loc of n_clouds int32, or c_null_ptr) on the host; points (dim, n) on the device; sample
+     !! (n_samples), sample_points (dim, n_samples), sample_sqdist (n_samples) and cover_sqdist (n_clouds) on the device, each
+     !! may be c_null_ptr
+     integer(c_int) function athena_mp_farthest_points(n_clouds, n, offsets, dim, points_dev, n_samples, sample_offsets, start, &
+          sample_dev, sample_points_dev, sample_sqdist_dev, cover_sqdist_dev) bind(C, name="athena_mp_farthest_points")
+       import :: c_int, c_int32_t, c_ptr
+       integer(c_int32_t), value :: n_clouds, n, dim, n_samples
+       integer(c_int32_t), intent(in) :: offsets(*), sample_offsets(*)
+       type(c_ptr), value :: points_dev, start, sample_dev, sample_points_dev, sample_sqdist_dev, cover_sqdist_dev
+     end function
+     !! the same with host arrays: points (dim, n) -> sample, sample_points, sample_sqdist, cover_sqdist (c_null_ptr: not wanted)
+     integer(c_int) function athena_mp_farthest_points_host(n_clouds, n, offsets, dim, points, n_samples, sample_offsets, start, &
+          sample, sample_points, sample_sqdist, cover_sqdist) bind(C, name="athena_mp_farthest_points_host")
+       import :: c_int, c_int32_t, c_float, c_ptr
+       integer(c_int32_t), value :: n_clouds, n, dim, n_samples
+       integer(c_int32_t), intent(in) :: offsets(*), sample_offsets(*)
+       real(c_float), intent(in) :: points(dim, *)
+       type(c_ptr), value :: start, sample, sample_points, sample_sqdist, cover_sqdist
+     end function
+     !! the last farthest-point call: samples, chunk tests of the stream route, tests that skipped, clouds on the stream route
+     integer(c_int) function athena_mp_fps_stats(out) bind(C, name="athena_mp_fps_stats")
+       import :: c_int, c_int64_t
+       integer(c_int64_t), intent(out) :: out(4)
      end function
      !! periodic structures -> pair list and edge geometry on the device, a batch per call (replaces get_graph_from_basis;
      !! definition: include/athena_mp.h).  offsets (n_structures + 1) and pbc (3) on the host; frac (3, n_atoms) and

@@ -14,7 +14,12 @@
     ... graph_nop_layer_type(local_term=False).backward(need_coord_grad=True) -> dcoords [E, d]
     g = point_sets_grad(handle, dcoords);  g["queries"] [n_queries, d], g["sources"] [n_sources, d]
 
-There is no autograd wrapper: these are the reverse steps themselves, to be called where the chain needs them."""
+There is no autograd wrapper: these are the reverse steps themselves, to be called where the chain needs them.
+
+Also the step that MAKES the second point set of from_point_sets / from_point_sets_knn (athena_amd/csrc/fps.hip):
+
+    sample, coarse, sample_offsets, cover = farthest_points(points, offsets, ratio=0.05)
+    handle, coords, eoff = DeviceGraph.from_point_sets(coarse, points, cover_radius(cover), sample_offsets, offsets)"""
 import ctypes as C
 
 import numpy as np
@@ -77,6 +82,77 @@ def point_sets_grad(handle, dcoords, want=("queries", "sources"), out=None):
     _capi.use_torch_stream()
     _capi.call("athena_mp_edge_grad_to_point_sets", handle.handle, dim, ptr(dcoords), ptr(res.get("queries")), ptr(res.get("sources")))
     return res
+
+
+def farthest_points(points, offsets=None, n_samples=None, ratio=None, start=None, want_sqdist=False, device=0):
+    """Farthest-point samples of a batch of point clouds on the device (athena_mp_farthest_points; the definition, term by term in
+    fp32 with ties to the smaller index, is in include/athena_mp.h).  points [n, dim] float32, dim 1..3: a numpy array, or a torch
+    tensor already on the device; offsets [B + 1] 0-based on the host (None: one cloud), empty clouds allowed.  Exactly one of
+    n_samples (an int for every cloud, or one per cloud) and ratio (m_b = min(n_b, max(1, ceil(ratio * n_b))) for a non-empty
+    cloud) is given; start: None, or [B] 1-based global indices of each cloud's first choice (0: its first point).  Returns
+    (sample, sample_points, sample_offsets, cover_sqdist) and, with want_sqdist, sample_sqdist last: sample int32 [m] = the chosen
+    points as 1-based global indices in selection order (every prefix of a cloud's samples is a sample of it), sample_points
+    [m, dim] their rows and cover_sqdist [B] float32 -- device tensors --, sample_offsets numpy int32 [B + 1], what
+    from_point_sets(..., query_offsets=...) takes."""
+    import torch
+
+    _capi.init(device)
+    dev = torch.device("cuda", device)
+    if isinstance(points, torch.Tensor):
+        pts = points.to(dev, torch.float32).contiguous()
+    else:
+        pts = torch.from_numpy(np.ascontiguousarray(points, dtype=np.float32)).to(dev)
+    if pts.dim() != 2:
+        raise ValueError("points must be [n, dim]")
+    n, dim = int(pts.shape[0]), int(pts.shape[1])
+    off = np.array([0, n], np.int32) if offsets is None else np.ascontiguousarray(offsets, dtype=np.int32)
+    if off.ndim != 1 or off.size < 1:
+        raise ValueError("offsets must be [B + 1]")
+    B = off.size - 1
+    sizes = np.diff(off.astype(np.int64))
+    if (n_samples is None) == (ratio is None):
+        raise ValueError("exactly one of n_samples and ratio must be given")
+    if ratio is not None:
+        if not ratio > 0:
+            raise ValueError("ratio must be positive")
+        m = np.where(sizes > 0, np.minimum(sizes, np.maximum(1, np.ceil(float(ratio) * sizes))), 0).astype(np.int64)
+    else:
+        m = np.broadcast_to(np.asarray(n_samples, dtype=np.int64), (B,)) if np.ndim(n_samples) == 0 else np.asarray(n_samples, np.int64)
+        if m.shape != (B,) or (m < 0).any():
+            raise ValueError("n_samples must be a non-negative int, or one per cloud")
+    if m.sum() >= 2 ** 31:
+        raise ValueError("more than 2^31 samples")
+    soff = np.concatenate([[0], np.cumsum(m)]).astype(np.int32)
+    st = None
+    if start is not None:
+        st = np.ascontiguousarray(start, dtype=np.int32)
+        if st.shape != (B,):
+            raise ValueError("start must hold one index per cloud")
+    mt = int(soff[-1])
+    sample = torch.empty((mt,), dtype=torch.int32, device=dev)
+    sample_points = torch.empty((mt, dim), dtype=torch.float32, device=dev)
+    sqdist = torch.empty((mt,), dtype=torch.float32, device=dev) if want_sqdist else None
+    cover = torch.empty((B,), dtype=torch.float32, device=dev)
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    vp = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+    _capi.use_torch_stream()
+    _capi.call("athena_mp_farthest_points", B, n, vp(off), dim, ptr(pts), mt, vp(soff), vp(st), ptr(sample), ptr(sample_points),
+               ptr(sqdist), ptr(cover))
+    out = (sample, sample_points, soff, cover)
+    return out + (sqdist,) if want_sqdist else out
+
+
+def cover_radius(cover_sqdist):
+    """The smallest float32 r with fl(r * r) >= max(cover_sqdist): sqrt, then nextafter upwards while short.  With this radius the
+    predicate of from_point_sets (s <= fl(r * r)) joins every point of every cloud to at least one of its samples."""
+    c = cover_sqdist.detach().cpu().numpy() if hasattr(cover_sqdist, "detach") else np.asarray(cover_sqdist)
+    c = np.float32(c.astype(np.float32).max()) if c.size else np.float32(0)
+    if not np.isfinite(c):
+        raise ValueError("cover_sqdist is not finite: a cloud with points got no sample, or its distances overflow")
+    r = np.sqrt(c, dtype=np.float32)
+    while np.float32(r * r) < c:
+        r = np.nextafter(r, np.float32(np.inf))
+    return float(r)
 
 
 def _host_tables(handle, lat_rows, offsets, edge_offsets, want):

@@ -291,6 +291,42 @@ int athena_mp_knn_graph_batched_host(int32_t n_clouds, int32_t n, const int32_t 
 /* What the search of the last k-nearest-neighbour call (one set or two) did: out[0] = query points, out[1] = candidates examined (distances
  * evaluated), out[2] = grid cells visited, out[3] = the largest shell (Chebyshev cell distance) any query reached. */
 int athena_mp_knn_stats(int64_t out[4]);
+/* Farthest-point sampling of a batch of point clouds on the device (fps.hip): m_b of a cloud's own points that cover it whatever
+ * its density -- the second point set of athena_mp_radius_pairs_bipartite / athena_mp_knn_pairs_bipartite (coarse onto fine, a mesh
+ * onto latent points, PointNet++ set abstraction) -- of which every prefix is a sample too, and the covering radius as a
+ * by-product.  Every implementation gives the same arrays.
+ *   Inputs: points [n, dim] fp32 row-major on the device, dim in 1..3; offsets [n_clouds + 1] int32 on the HOST, 0-based, as in
+ *   athena_mp_radius_pairs_batched (empty clouds allowed); sample_offsets [n_clouds + 1] int32 on the HOST, 0-based, ascending from
+ *   0 to n_samples: cloud b gets m_b = sample_offsets[b+1] - sample_offsets[b] samples, 0 <= m_b <= n_b; start [n_clouds] int32 on
+ *   the HOST, 1-based global indices, or NULL: entry b is used only when m_b > 0 and must then lie in cloud b; NULL, or an entry of
+ *   0, means the cloud's first point.
+ *   Distance: s(i, j) is the squared distance of athena_mp_radius_pairs, unchanged: d = p_i - p_j per component,
+ *   s = ((d0*d0) + d1*d1) + d2*d2, every operation rounded to fp32 on its own.  An overflow is +inf; finite inputs never give NaN.
+ *   Selection, per cloud: dmin[j] = +inf for every point; step 1 chooses start; after choosing c, dmin[j] = min(dmin[j], s(j, c))
+ *   for every j of the cloud; the next step chooses, among the points NOT YET CHOSEN, the largest dmin, ties to the SMALLER index.
+ *   So coincident points are chosen last, in index order, and a lattice, or distances that overflow, is decided by the index.
+ *   Outputs, on the device, each may be NULL alone: sample [n_samples] int32 = the chosen points as 1-based global indices in
+ *   selection order, cloud after cloud; sample_points [n_samples, dim] = their rows, bit for bit; sample_sqdist [n_samples] = the
+ *   chosen point's dmin at the moment it was chosen: +inf for a cloud's first sample, non-increasing after it; cover_sqdist
+ *   [n_clouds] = the largest dmin[j] over ALL points of the cloud after the last update: +inf when n_b > 0 = m_b, 0 for an empty
+ *   cloud.  Its square root, rounded up, is the radius with which athena_mp_radius_pairs_bipartite (samples as queries) leaves no
+ *   point of the cloud without a sample.
+ * Refused with a message: dim outside 1..3; n_clouds < 0; for either offset array, named, the offset errors of
+ * athena_mp_radius_pairs_bipartite; m_b > n_b (the cloud is named); a start outside its cloud; a non-finite coordinate (cloud,
+ * component and point of the first one are named, 1-based).  The library stays usable after a refusal.  Two calls on the same input
+ * are byte-identical.  Cost: one cloud is sampled by ONE workgroup, its m_b steps in one launch; a batch of clouds fills the device,
+ * one large cloud runs on one compute unit. */
+int athena_mp_farthest_points(int32_t n_clouds, int32_t n, const int32_t *offsets_host, int32_t dim, const float *points_dev,
+                              int32_t n_samples, const int32_t *sample_offsets_host, const int32_t *start_host, int32_t *sample_dev,
+                              float *sample_points_dev, float *sample_sqdist_dev, float *cover_sqdist_dev);
+/* The same with every array on the host, for callers that hold Fortran arrays; each output may be NULL alone. */
+int athena_mp_farthest_points_host(int32_t n_clouds, int32_t n, const int32_t *offsets_host, int32_t dim, const float *points_host,
+                                   int32_t n_samples, const int32_t *sample_offsets_host, const int32_t *start_host,
+                                   int32_t *sample_out, float *sample_points_out, float *sample_sqdist_out, float *cover_sqdist_out);
+/* What the last farthest-point call did: out[0] = samples chosen, out[1] = chunk tests of the stream route (a chunk is 64 points of
+ * a cloud too large for the register route; one test per chunk and step), out[2] = the tests that skipped their chunk, out[3] =
+ * clouds that took the stream route. */
+int athena_mp_fps_stats(int64_t out[4]);
 /* Periodic structures -> neighbour graphs on the device, a batch per call (periodic_graph.hip).  It replaces get_graph_from_basis
  * of the reference's chemical examples (example/example_library/src/mod_read_chemical_graphs.f90:196-278); the step in front of
  * athena_mp_graph_create_from_edges_dev.
