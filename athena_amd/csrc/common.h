@@ -203,6 +203,8 @@ int points_grad_check(const athena_mp_graph *g, int32_t dim);
 int point_sets_grad_check(const athena_mp_graph *g, int32_t dim, bool want_queries, bool want_sources);
 int periodic_grad_check(const athena_mp_graph *g, int32_t B, int32_t n, const int32_t *offsets, const int64_t *edge_offsets,
                         float cutoff_max, bool has_dfeature, int32_t fe_cols, bool has_dvec);
+// argument checks of the interpolation entries (interp.hip), shared with their *_host forms; dim, F, eps: null where the entry takes none
+int interp_check(const char *who, const athena_mp_graph *g, const int32_t *dim, const int32_t *F, const float *eps);
 void graph_cache_clear(); // idle and live handles of athena_mp_graph_acquire (capi.hip)
 void host_pool_release();   // staging buffers of the *_host entry points (host.hip)
 uint64_t content_hash(const void *p, size_t bytes);   // every byte of a host array (capi.hip)

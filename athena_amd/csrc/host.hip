@@ -670,6 +670,40 @@ int athena_mp_edge_grad_to_point_sets_host(const athena_mp_graph *g, int32_t dim
                                                                dsources ? (float *)p[2] : nullptr);
                   });
 }
+// ---- inverse-distance interpolation (interp.hip): weights, then the gather; weights, the gather, then both gradients -------------
+int athena_mp_interp_host(const athena_mp_graph *g, int32_t dim, int32_t F, const float *coords, float eps, const float *x, float *y,
+                          float *weights)
+{
+    if (int rc = interp_check("interp_host", g, &dim, &F, &eps)) return rc;
+    const int64_t E = g->n_edge_cols;
+    AMP_REQUIRE((E == 0 || (coords && x)) && (g->n_rows == 0 || y), "interp_host: null array");
+    // the weights live in HBM whether the caller wants them or not: an absent output is a buffer that goes nowhere
+    return staged({{coords, nullptr, fb(E, dim)}, {x, nullptr, fb(g->n_cols, F)}, {nullptr, y, fb(g->n_rows, F)}, {nullptr, weights, fb(E, 1)}},
+                  [&](std::vector<void *> &p) {
+                      if (int rc = athena_mp_interp_weights(g, dim, (float *)p[0], eps, (float *)p[3], nullptr)) return rc;
+                      return athena_mp_interp_fwd(g, F, (float *)p[3], (float *)p[1], (float *)p[2]);
+                  });
+}
+int athena_mp_interp_bwd_host(const athena_mp_graph *g, int32_t dim, int32_t F, const float *coords, float eps, const float *x,
+                              const float *dy, float *dx, float *dcoords)
+{
+    if (int rc = interp_check("interp_bwd_host", g, &dim, &F, &eps)) return rc;
+    const int64_t E = g->n_edge_cols;
+    AMP_REQUIRE((E == 0 || (coords && x)) && (g->n_rows == 0 || dy), "interp_bwd_host: null array");
+    AMP_REQUIRE(dx || dcoords, "interp_bwd_host: dx and dcoords are both null: nothing to compute");
+    auto out = [](float *h, size_t bytes) { return Stage{nullptr, h, h ? bytes : 0, true}; };
+    return staged({{coords, nullptr, fb(E, dim)}, {x, nullptr, fb(g->n_cols, F)}, {dy, nullptr, fb(g->n_rows, F)}, out(dx, fb(g->n_cols, F)),
+                   out(dcoords, fb(E, dim)), {nullptr, nullptr, fb(E, 1)}, {nullptr, nullptr, dcoords ? fb(g->n_rows, F) : 0}},
+                  [&](std::vector<void *> &p) {
+                      float *w = (float *)p[5], *yd = (float *)p[6];
+                      if (int rc = athena_mp_interp_weights(g, dim, (float *)p[0], eps, w, nullptr)) return rc;
+                      if (dx)
+                          if (int rc = athena_mp_interp_bwd_x(g, F, w, (float *)p[2], (float *)p[3])) return rc;
+                      if (!dcoords) return 0;
+                      if (int rc = athena_mp_interp_fwd(g, F, w, (float *)p[1], yd)) return rc;
+                      return athena_mp_interp_bwd_coords(g, dim, F, (float *)p[0], eps, w, (float *)p[1], yd, (float *)p[2], (float *)p[4]);
+                  });
+}
 int athena_mp_periodic_grad_host(const athena_mp_graph *g, int32_t B, int32_t n, const int32_t *offsets, const int64_t *edge_offsets,
                                  const float *lat, float cutoff_max, const float *vec, const float *dfeature, int32_t fe_cols,
                                  const float *dvec, float *dcart, float *dfrac, float *virial, float *dlat)

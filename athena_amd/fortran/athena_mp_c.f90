@@ -57,6 +57,8 @@ module athena_mp_c
   public :: athena_mp_knn_pairs_batched, athena_mp_knn_pairs, athena_mp_knn_graph_batched_host, athena_mp_knn_stats
   public :: athena_mp_knn_pairs_bipartite, athena_mp_knn_graph_bipartite_host
   public :: athena_mp_farthest_points, athena_mp_farthest_points_host, athena_mp_fps_stats
+  public :: athena_mp_interp_weights, athena_mp_interp_fwd, athena_mp_interp_bwd_x, athena_mp_interp_bwd_coords
+  public :: athena_mp_interp_host, athena_mp_interp_bwd_host
   public :: athena_mp_periodic_pairs, athena_mp_periodic_graph_host, athena_mp_periodic_stats
   public :: athena_mp_edge_grad_to_points, athena_mp_periodic_grad
   public :: athena_mp_edge_grad_to_points_host, athena_mp_periodic_grad_host
@@ -772,6 +774,53 @@ module athena_mp_c
        type(c_ptr), value :: graph, dqueries, dsources
        integer(c_int32_t), value :: dim
        real(c_float), intent(in) :: dcoords(dim, *)
+     end function
+     !! inverse-distance interpolation over a two-set handle (definition: include/athena_mp.h): the weights of coords (dim, E) ->
+     !! weights (E), wsum (n_rows) or c_null_ptr
+     integer(c_int) function athena_mp_interp_weights(graph, dim, coords_dev, eps, weights_dev, wsum_dev) &
+          bind(C, name="athena_mp_interp_weights")
+       import :: c_int, c_int32_t, c_float, c_ptr
+       type(c_ptr), value :: graph, coords_dev, weights_dev, wsum_dev
+       integer(c_int32_t), value :: dim
+       real(c_float), value :: eps
+     end function
+     !! the weighted gather over the rows, x (F, n_cols) -> y (F, n_rows), for any weights (E) ...
+     integer(c_int) function athena_mp_interp_fwd(graph, F, weights_dev, x_dev, y_dev) bind(C, name="athena_mp_interp_fwd")
+       import :: c_int, c_int32_t, c_ptr
+       type(c_ptr), value :: graph, weights_dev, x_dev, y_dev
+       integer(c_int32_t), value :: F
+     end function
+     !! ... and over the columns, dy (F, n_rows) -> dx (F, n_cols)
+     integer(c_int) function athena_mp_interp_bwd_x(graph, F, weights_dev, dy_dev, dx_dev) bind(C, name="athena_mp_interp_bwd_x")
+       import :: c_int, c_int32_t, c_ptr
+       type(c_ptr), value :: graph, weights_dev, dy_dev, dx_dev
+       integer(c_int32_t), value :: F
+     end function
+     !! the gradient with respect to coords through the weights: dcoords (dim, E), what athena_mp_edge_grad_to_point_sets takes
+     integer(c_int) function athena_mp_interp_bwd_coords(graph, dim, F, coords_dev, eps, weights_dev, x_dev, y_dev, dy_dev, &
+          dcoords_dev) bind(C, name="athena_mp_interp_bwd_coords")
+       import :: c_int, c_int32_t, c_float, c_ptr
+       type(c_ptr), value :: graph, coords_dev, weights_dev, x_dev, y_dev, dy_dev, dcoords_dev
+       integer(c_int32_t), value :: dim, F
+       real(c_float), value :: eps
+     end function
+     !! the same with host arrays (staged): coords (dim, E), x (F, n_cols) -> y (F, n_rows); weights: c_loc of (E), or c_null_ptr
+     integer(c_int) function athena_mp_interp_host(graph, dim, F, coords, eps, x, y, weights) bind(C, name="athena_mp_interp_host")
+       import :: c_int, c_int32_t, c_float, c_ptr
+       type(c_ptr), value :: graph, weights
+       integer(c_int32_t), value :: dim, F
+       real(c_float), value :: eps
+       real(c_float), intent(in) :: coords(dim, *), x(F, *)
+       real(c_float), intent(inout) :: y(F, *)
+     end function
+     !! ... and dy (F, n_rows) -> dx (F, n_cols), dcoords (dim, E): c_loc of the host arrays, or c_null_ptr (not both)
+     integer(c_int) function athena_mp_interp_bwd_host(graph, dim, F, coords, eps, x, dy, dx, dcoords) &
+          bind(C, name="athena_mp_interp_bwd_host")
+       import :: c_int, c_int32_t, c_float, c_ptr
+       type(c_ptr), value :: graph, dx, dcoords
+       integer(c_int32_t), value :: dim, F
+       real(c_float), value :: eps
+       real(c_float), intent(in) :: coords(dim, *), x(F, *), dy(F, *)
      end function
      !! ... dfeature, dvec and the four outputs passed as c_loc of host arrays, or c_null_ptr
      integer(c_int) function athena_mp_periodic_grad_host(graph, n_structures, n_atoms, offsets, edge_offsets, lat, cutoff_max, &

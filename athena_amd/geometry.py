@@ -19,7 +19,20 @@ There is no autograd wrapper: these are the reverse steps themselves, to be call
 Also the step that MAKES the second point set of from_point_sets / from_point_sets_knn (athena_amd/csrc/fps.hip):
 
     sample, coarse, sample_offsets, cover = farthest_points(points, offsets, ratio=0.05)
-    handle, coords, eoff = DeviceGraph.from_point_sets(coarse, points, cover_radius(cover), sample_offsets, offsets)"""
+    handle, coords, eoff = DeviceGraph.from_point_sets(coarse, points, cover_radius(cover), sample_offsets, offsets)
+
+And the way back, coarse to fine (athena_amd/csrc/interp.hip): inverse-distance interpolation of the coarse set's features onto the
+fine points, and its reverse steps down to both point sets:
+
+    sample, coarse, sample_offsets, cover = farthest_points(points, offsets, ratio=0.05)
+    handle, coords, eoff = DeviceGraph.from_point_sets_knn(points, coarse, k=3, query_offsets=offsets, source_offsets=sample_offsets)
+    weights, wsum = interp_weights(handle, coords)                      # [E], [n_points]
+    y = interpolate(handle, weights, x_coarse)                          # [n_points, F]
+    ... the layers above return dy [n_points, F]
+    g = interpolate_grad(handle, coords, weights, x_coarse, y, dy)      # g["x"] [n_coarse, F], g["coords"] [E, d]
+    p = point_sets_grad(handle, g["coords"]);  p["queries"], p["sources"]
+
+interpolate and interpolate_grad(want=("x",)) take ANY weights [E]: mean pooling and quadrature-weighted transfer are the same calls."""
 import ctypes as C
 
 import numpy as np
@@ -81,6 +94,92 @@ def point_sets_grad(handle, dcoords, want=("queries", "sources"), out=None):
     ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
     _capi.use_torch_stream()
     _capi.call("athena_mp_edge_grad_to_point_sets", handle.handle, dim, ptr(dcoords), ptr(res.get("queries")), ptr(res.get("sources")))
+    return res
+
+
+def _device_f32(t, shape, what):
+    """t is a contiguous float32 device tensor of this shape (None in a place: any size), or ValueError"""
+    import torch
+
+    ok = isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.dim() == len(shape)
+    if not (ok and all(want is None or int(have) == want for have, want in zip(t.shape, shape))):
+        raise ValueError(f"{what} must be a contiguous float32 device tensor [{', '.join('*' if s is None else str(s) for s in shape)}]")
+    return t
+
+
+def interp_weights(handle, coords, eps=1e-16, out=None):
+    """Inverse-squared-distance weights over a two-set handle (athena_mp_interp_weights; the definition, term by term in fp32, is in
+    include/athena_mp.h): handle and coords [E, dim] as DeviceGraph.from_point_sets / from_point_sets_knn returned them.  Returns
+    (weights [E], wsum [n_queries]) float32 on the device: w_e = 1 / max(|coords[e]|^2, eps), wsum[i] = the sum of w over row i in
+    CSR order, weights[e] = w_e / wsum[i] (0 along a row whose sum is 0): each non-empty row's weights add up to 1 but for rounding.
+    eps: finite, at least 2^-60.  out: a (weights, wsum) pair of contiguous float32 device tensors to write into."""
+    import torch
+
+    E, n = handle.n_edge_cols, handle.n_rows
+    coords = _device_f32(coords, (E, None), "coords")
+    dim = int(coords.shape[1])
+    if out is None:
+        out = (torch.empty((E,), dtype=torch.float32, device=coords.device), torch.empty((n,), dtype=torch.float32, device=coords.device))
+    weights, wsum = _device_f32(out[0], (E,), "out[0]"), _device_f32(out[1], (n,), "out[1]")
+    _capi.use_torch_stream()
+    _capi.call("athena_mp_interp_weights", handle.handle, dim, C.c_void_p(coords.data_ptr()), float(eps), C.c_void_p(weights.data_ptr()),
+               C.c_void_p(wsum.data_ptr()))
+    return weights, wsum
+
+
+def interpolate(handle, weights, x, out=None):
+    """y [n_queries, F] = the weighted sum over each row of the handle (athena_mp_interp_fwd): y[i] = sum over the entries (j, e) of
+    row i in CSR order of weights[e] * x[j], bit for bit the sequential fp32 sum; an empty row gives 0.  weights [E] and x
+    [n_sources, F]: contiguous float32 device tensors; any weights, not only interp_weights'.  out: a contiguous float32 device
+    tensor [n_queries, F] to write into."""
+    import torch
+
+    weights = _device_f32(weights, (handle.n_edge_cols,), "weights")
+    x = _device_f32(x, (handle.n_cols, None), "x")
+    F = int(x.shape[1])
+    if out is None:
+        out = torch.empty((handle.n_rows, F), dtype=torch.float32, device=x.device)
+    out = _device_f32(out, (handle.n_rows, F), "out")
+    _capi.use_torch_stream()
+    _capi.call("athena_mp_interp_fwd", handle.handle, F, C.c_void_p(weights.data_ptr()), C.c_void_p(x.data_ptr()), C.c_void_p(out.data_ptr()))
+    return out
+
+
+def interpolate_grad(handle, coords, weights, x, y, dy, eps=1e-16, want=("x", "coords"), out=None):
+    """The reverse of interpolate, and of interp_weights under it (athena_mp_interp_bwd_x, athena_mp_interp_bwd_coords): dy
+    [n_queries, F] -> a dict of device tensors for the names in `want`: "x" [n_sources, F], row j = the sum over the handle's column
+    j, queries ascending, of weights[e] * dy[i], bit for bit the sequential sum; "coords" [E, dim], the gradient with respect to
+    coords through the weights of interp_weights(handle, coords, eps) -- exactly 0 where the clamp held --, which point_sets_grad
+    takes as it is.  coords, weights, x and y as the forward calls took and returned them ("x" alone needs only weights and dy:
+    coords, x and y may then be None).  out: a dict of contiguous float32 device tensors to write into, by the same names."""
+    import torch
+
+    want = tuple(want)
+    if not want or any(w not in ("x", "coords") for w in want):
+        raise ValueError('want must name some of ("x", "coords")')
+    E, nq, ns = handle.n_edge_cols, handle.n_rows, handle.n_cols
+    weights = _device_f32(weights, (E,), "weights")
+    dy = _device_f32(dy, (nq, None), "dy")
+    F = int(dy.shape[1])
+    dim = None
+    if "coords" in want:
+        coords = _device_f32(coords, (E, None), "coords")
+        dim = int(coords.shape[1])
+        x, y = _device_f32(x, (ns, F), "x"), _device_f32(y, (nq, F), "y")
+    shapes = {"x": (ns, F), "coords": (E, dim)}
+    res = {}
+    for w in want:
+        t = None if out is None else out.get(w)
+        if t is None:
+            t = torch.empty(shapes[w], dtype=torch.float32, device=dy.device)
+        res[w] = _device_f32(t, shapes[w], f"out[{w!r}]")
+    ptr = lambda t: C.c_void_p(t.data_ptr())
+    _capi.use_torch_stream()
+    if "x" in want:
+        _capi.call("athena_mp_interp_bwd_x", handle.handle, F, ptr(weights), ptr(dy), ptr(res["x"]))
+    if "coords" in want:
+        _capi.call("athena_mp_interp_bwd_coords", handle.handle, dim, F, ptr(coords), float(eps), ptr(weights), ptr(x), ptr(y), ptr(dy),
+                   ptr(res["coords"]))
     return res
 
 

@@ -417,7 +417,54 @@ int athena_mp_periodic_grad(const athena_mp_graph *g, int32_t n_structures, int3
 int athena_mp_edge_grad_to_point_sets(const athena_mp_graph *g, int32_t dim, const float *dcoords_dev, float *dqueries_dev,
                                       float *dsources_dev);
 int athena_mp_edge_grad_to_point_sets_host(const athena_mp_graph *g, int32_t dim, const float *dcoords, float *dqueries, float *dsources);
-/* The same two with every array on the host (a handle plus Fortran arrays), staged through HBM */
+/* Inverse-distance interpolation over a two-set graph, with its gradients (interp.hip): features carried from the sources to the
+ * queries of athena_mp_radius_pairs_bipartite / athena_mp_knn_pairs_bipartite -- the feature propagation of PointNet++, the skip path
+ * of a U-shaped operator's decoder, plain k-nearest-neighbour interpolation -- and, under it, a gather over a handle's CSR with
+ * caller-supplied per-edge weights, forward and transposed (mean pooling onto samples and quadrature-weighted transfer are the same
+ * call with other weights).  Nothing in the reference corresponds to them.
+ * Definition.  All arithmetic is fp32, every operation rounded on its own, / correctly rounded, subnormals kept.  g is a rectangular
+ * handle of athena_mp_graph_create_bipartite_dev (from either builder), E its edge columns; coords [E, dim] is what the builder
+ * wrote, coords[e] = q_i - p_j, dim in 1..3.  Row i of the handle is its forward CSR as athena_mp_graph_export shows it (rowptr,
+ * col, eid), column j its transposed CSR (t_rowptr, t_src, t_eid: queries ascending); those orders are the summation orders.
+ *   Weights (athena_mp_interp_weights), d = coords[e]:
+ *     s_e = ((d0 * d0) + d1 * d1) + d2 * d2: the builder's own expression, so s_e is its sqdist bit for bit
+ *     w_e = 1 / m_e, m_e = eps where s_e <= eps, else s_e (max(s_e, eps); a NaN stays one); an s that overflowed gives w = +0
+ *     W_i = +0; for k = rowptr[i] .. rowptr[i+1]-1 in order: W_i = W_i + w_eid[k]
+ *     weights[e] = w_e / W_i for the edges of row i, +0 for every edge of a row whose W_i is 0;  wsum[i] = W_i (wsum may be NULL)
+ *   Every element of both outputs is written; an empty row gives wsum = +0.  eps must be finite and at least 2^-60: then W cannot
+ *   overflow, and weights[e] <= 1 because round-to-nearest sums of non-negative terms are monotone.
+ *   Weighted gather, for ANY weights [E], not only the ones above:
+ *     athena_mp_interp_fwd    x [n_cols, F] -> y [n_rows, F]:  acc = +0; for k = rowptr[i] .. in order:
+ *                             acc = acc + weights[eid[k]] * x[col[k], f];  y[i, f] = acc
+ *     athena_mp_interp_bwd_x  dy [n_rows, F] -> dx [n_cols, F]:  acc = +0; for k = t_rowptr[j] .. in order:
+ *                             acc = acc + weights[t_eid[k]] * dy[t_src[k], f];  dx[j, f] = acc
+ *   Arrays are row-major.  An empty row or column gives +0; every element is written; no atomics: two runs are byte-identical.
+ *   Coordinate gradient (athena_mp_interp_bwd_coords), y the forward result, per edge e = (i, j):
+ *     g_e = sum over f of dy[i, f] * (x[j, f] - y[i, f])   (the order of this sum is free: the one output that is not bit-defined)
+ *     t_e = -(weights[e] * w_e) * g_e;  dcoords[e, c] = (2 * d_c) * t_e
+ *   dcoords[e, :] is exactly +0 where s_e <= eps (the clamp) or w_e = 0.  The result is the gradient with respect to coords for
+ *   weights made by athena_mp_interp_weights with the same eps, and feeds athena_mp_edge_grad_to_point_sets unchanged.
+ * Every edge column must be carried by exactly one entry, which is what athena_mp_graph_create_bipartite_dev builds: each weights[e]
+ * and dcoords[e, :] then has one writer.
+ * Refused with a message: a handle without edge columns; an entry that carries no edge id; more or fewer entries than edge columns;
+ * dim outside 1..3; F < 1; an eps that is not finite or below 2^-60.  The library stays usable after a refusal.  E = 0, n_rows = 0 and n_cols = 0 succeed (empty arrays may
+ * be NULL).  Values are not scanned: NaN propagates.  A caller's pointer needs only the alignment of a float. */
+int athena_mp_interp_weights(const athena_mp_graph *g, int32_t dim, const float *coords_dev, float eps, float *weights_dev,
+                             float *wsum_dev);
+int athena_mp_interp_fwd(const athena_mp_graph *g, int32_t F, const float *weights_dev, const float *x_dev, float *y_dev);
+int athena_mp_interp_bwd_x(const athena_mp_graph *g, int32_t F, const float *weights_dev, const float *dy_dev, float *dx_dev);
+int athena_mp_interp_bwd_coords(const athena_mp_graph *g, int32_t dim, int32_t F, const float *coords_dev, float eps,
+                                const float *weights_dev, const float *x_dev, const float *y_dev, const float *dy_dev,
+                                float *dcoords_dev);
+/* The same for callers that hold Fortran arrays, staged through HBM.  athena_mp_interp_host: the weights of coords, then y; weights
+ * [E] may be NULL.  athena_mp_interp_bwd_host: the weights and y again, then dx [n_cols, F] and dcoords [E, dim]; each may be NULL,
+ * not both. */
+int athena_mp_interp_host(const athena_mp_graph *g, int32_t dim, int32_t F, const float *coords, float eps, const float *x, float *y,
+                          float *weights);
+int athena_mp_interp_bwd_host(const athena_mp_graph *g, int32_t dim, int32_t F, const float *coords, float eps, const float *x,
+                              const float *dy, float *dx, float *dcoords);
+/* athena_mp_edge_grad_to_points and athena_mp_periodic_grad with every array on the host (a handle plus Fortran arrays), staged
+ * through HBM */
 int athena_mp_edge_grad_to_points_host(const athena_mp_graph *g, int32_t dim, const float *dcoords, float *dpoints);
 int athena_mp_periodic_grad_host(const athena_mp_graph *g, int32_t n_structures, int32_t n_atoms, const int32_t *offsets,
                                  const int64_t *edge_offsets, const float *lat, float cutoff_max, const float *vec,
