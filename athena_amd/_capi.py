@@ -73,6 +73,12 @@ _PROTOS = {
     "athena_mp_interp_bwd_coords": [_vp, _i32, _i32, _vp, _f32, _vp, _vp, _vp, _vp, _vp],
     "athena_mp_interp_host": [_vp, _i32, _i32, _vp, _f32, _vp, _vp, _vp],
     "athena_mp_interp_bwd_host": [_vp, _i32, _i32, _vp, _f32, _vp, _vp, _vp, _vp],
+    "athena_mp_pool_max_fwd": [_vp, _i32, _vp, _vp, _vp],
+    "athena_mp_pool_max_edges_fwd": [_vp, _i32, _vp, _vp, _vp],
+    "athena_mp_pool_max_bwd_x": [_vp, _i32, _vp, _vp, _vp],
+    "athena_mp_pool_max_bwd_edges": [_vp, _i32, _vp, _vp, _vp],
+    "athena_mp_pool_max_host": [_vp, _i32, _vp, _vp, _vp, _vp],
+    "athena_mp_pool_max_bwd_host": [_vp, _i32, _vp, _vp, _vp, _vp],
     "athena_mp_graph_export": [_vp, _i32, _vp, _i64, _vp],
     "athena_mp_graph_destroy": [_vp],
     "athena_mp_graph_key": [_i32, _i64, _vp, _vp, C.POINTER(C.c_uint64)],

@@ -205,6 +205,8 @@ int periodic_grad_check(const athena_mp_graph *g, int32_t B, int32_t n, const in
                         float cutoff_max, bool has_dfeature, int32_t fe_cols, bool has_dvec);
 // argument checks of the interpolation entries (interp.hip), shared with their *_host forms; dim, F, eps: null where the entry takes none
 int interp_check(const char *who, const athena_mp_graph *g, const int32_t *dim, const int32_t *F, const float *eps);
+// argument checks of the max-pooling entries (pool.hip), shared with their *_host forms; the edge forms add interp_check's conditions
+int pool_check(const char *who, const athena_mp_graph *g, int32_t F, bool edge_form);
 void graph_cache_clear(); // idle and live handles of athena_mp_graph_acquire (capi.hip)
 void host_pool_release();   // staging buffers of the *_host entry points (host.hip)
 uint64_t content_hash(const void *p, size_t bytes);   // every byte of a host array (capi.hip)

@@ -704,6 +704,34 @@ int athena_mp_interp_bwd_host(const athena_mp_graph *g, int32_t dim, int32_t F, 
                       return athena_mp_interp_bwd_coords(g, dim, F, (float *)p[0], eps, w, (float *)p[1], yd, (float *)p[2], (float *)p[4]);
                   });
 }
+// ---- max pooling (pool.hip): one forward of either form; the reverse steps that were asked for, from the one arg -----------------
+int athena_mp_pool_max_host(const athena_mp_graph *g, int32_t F, const float *x, const float *h, float *y, int32_t *arg)
+{
+    AMP_REQUIRE((x != nullptr) != (h != nullptr), "pool_max_host: exactly one of x (the vertex form) and h (the edge form) must be given");
+    const bool edges = h != nullptr;
+    if (int rc = pool_check("pool_max_host", g, F, edges)) return rc;
+    AMP_REQUIRE(g->n_rows == 0 || y, "pool_max_host: null array");
+    // arg lives in HBM whether the caller wants it or not: an absent output is a buffer that goes nowhere
+    return staged({{edges ? h : x, nullptr, fb(edges ? g->n_edge_cols : g->n_cols, F)}, {nullptr, y, fb(g->n_rows, F)},
+                   {nullptr, arg, fb(g->n_rows, F)}},
+                  [&](std::vector<void *> &p) {
+                      return edges ? athena_mp_pool_max_edges_fwd(g, F, (float *)p[0], (float *)p[1], (int32_t *)p[2])
+                                   : athena_mp_pool_max_fwd(g, F, (float *)p[0], (float *)p[1], (int32_t *)p[2]);
+                  });
+}
+int athena_mp_pool_max_bwd_host(const athena_mp_graph *g, int32_t F, const int32_t *arg, const float *dy, float *dx, float *dh)
+{
+    AMP_REQUIRE(dx || dh, "pool_max_bwd_host: dx and dh are both null: nothing to compute");
+    if (int rc = pool_check("pool_max_bwd_host", g, F, dh != nullptr)) return rc;
+    AMP_REQUIRE(g->nnz == 0 || (arg && dy), "pool_max_bwd_host: null array");
+    auto out = [](float *host, size_t bytes) { return Stage{nullptr, host, host ? bytes : 0, true}; };
+    return staged({{arg, nullptr, fb(g->n_rows, F)}, {dy, nullptr, fb(g->n_rows, F)}, out(dx, fb(g->n_cols, F)), out(dh, fb(g->n_edge_cols, F))},
+                  [&](std::vector<void *> &p) {
+                      if (dx)
+                          if (int rc = athena_mp_pool_max_bwd_x(g, F, (int32_t *)p[0], (float *)p[1], (float *)p[2])) return rc;
+                      return dh ? athena_mp_pool_max_bwd_edges(g, F, (int32_t *)p[0], (float *)p[1], (float *)p[3]) : 0;
+                  });
+}
 int athena_mp_periodic_grad_host(const athena_mp_graph *g, int32_t B, int32_t n, const int32_t *offsets, const int64_t *edge_offsets,
                                  const float *lat, float cutoff_max, const float *vec, const float *dfeature, int32_t fe_cols,
                                  const float *dvec, float *dcart, float *dfrac, float *virial, float *dlat)

@@ -59,6 +59,8 @@ module athena_mp_c
   public :: athena_mp_farthest_points, athena_mp_farthest_points_host, athena_mp_fps_stats
   public :: athena_mp_interp_weights, athena_mp_interp_fwd, athena_mp_interp_bwd_x, athena_mp_interp_bwd_coords
   public :: athena_mp_interp_host, athena_mp_interp_bwd_host
+  public :: athena_mp_pool_max_fwd, athena_mp_pool_max_edges_fwd, athena_mp_pool_max_bwd_x, athena_mp_pool_max_bwd_edges
+  public :: athena_mp_pool_max_host, athena_mp_pool_max_bwd_host
   public :: athena_mp_periodic_pairs, athena_mp_periodic_graph_host, athena_mp_periodic_stats
   public :: athena_mp_edge_grad_to_points, athena_mp_periodic_grad
   public :: athena_mp_edge_grad_to_points_host, athena_mp_periodic_grad_host
@@ -821,6 +823,49 @@ module athena_mp_c
        integer(c_int32_t), value :: dim, F
        real(c_float), value :: eps
        real(c_float), intent(in) :: coords(dim, *), x(F, *), dy(F, *)
+     end function
+     !! max pooling over a handle's rows with its arg-max (definition: include/athena_mp.h): x (F, n_cols) -> y (F, n_rows) and
+     !! arg (F, n_rows) int32, the 0-based column of the first maximum, -1 along an empty row; arg_dev may be c_null_ptr
+     integer(c_int) function athena_mp_pool_max_fwd(graph, F, x_dev, y_dev, arg_dev) bind(C, name="athena_mp_pool_max_fwd")
+       import :: c_int, c_int32_t, c_ptr
+       type(c_ptr), value :: graph, x_dev, y_dev, arg_dev
+       integer(c_int32_t), value :: F
+     end function
+     !! ... the same over per-edge values h (F, E), on a handle with one entry per edge column
+     integer(c_int) function athena_mp_pool_max_edges_fwd(graph, F, h_dev, y_dev, arg_dev) &
+          bind(C, name="athena_mp_pool_max_edges_fwd")
+       import :: c_int, c_int32_t, c_ptr
+       type(c_ptr), value :: graph, h_dev, y_dev, arg_dev
+       integer(c_int32_t), value :: F
+     end function
+     !! the reverse of the vertex form: dy (F, n_rows) -> dx (F, n_cols), each column's sum over the rows that chose it, ascending
+     integer(c_int) function athena_mp_pool_max_bwd_x(graph, F, arg_dev, dy_dev, dx_dev) bind(C, name="athena_mp_pool_max_bwd_x")
+       import :: c_int, c_int32_t, c_ptr
+       type(c_ptr), value :: graph, arg_dev, dy_dev, dx_dev
+       integer(c_int32_t), value :: F
+     end function
+     !! the reverse of the edge form: dy (F, n_rows) -> dh (F, E), dy of the row where the edge was chosen, else 0
+     integer(c_int) function athena_mp_pool_max_bwd_edges(graph, F, arg_dev, dy_dev, dh_dev) &
+          bind(C, name="athena_mp_pool_max_bwd_edges")
+       import :: c_int, c_int32_t, c_ptr
+       type(c_ptr), value :: graph, arg_dev, dy_dev, dh_dev
+       integer(c_int32_t), value :: F
+     end function
+     !! the same with host arrays (staged): exactly one of x (F, n_cols) and h (F, E) is c_loc of the host array, the other
+     !! c_null_ptr; arg: c_loc of (F, n_rows) int32, or c_null_ptr
+     integer(c_int) function athena_mp_pool_max_host(graph, F, x, h, y, arg) bind(C, name="athena_mp_pool_max_host")
+       import :: c_int, c_int32_t, c_float, c_ptr
+       type(c_ptr), value :: graph, x, h, arg
+       integer(c_int32_t), value :: F
+       real(c_float), intent(inout) :: y(F, *)
+     end function
+     !! ... and arg, dy (F, n_rows) -> dx (F, n_cols), dh (F, E): c_loc of the host arrays, or c_null_ptr (not both)
+     integer(c_int) function athena_mp_pool_max_bwd_host(graph, F, arg, dy, dx, dh) bind(C, name="athena_mp_pool_max_bwd_host")
+       import :: c_int, c_int32_t, c_float, c_ptr
+       type(c_ptr), value :: graph, dx, dh
+       integer(c_int32_t), value :: F
+       integer(c_int32_t), intent(in) :: arg(F, *)
+       real(c_float), intent(in) :: dy(F, *)
      end function
      !! ... dfeature, dvec and the four outputs passed as c_loc of host arrays, or c_null_ptr
      integer(c_int) function athena_mp_periodic_grad_host(graph, n_structures, n_atoms, offsets, edge_offsets, lat, cutoff_max, &

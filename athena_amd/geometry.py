@@ -32,7 +32,20 @@ fine points, and its reverse steps down to both point sets:
     g = interpolate_grad(handle, coords, weights, x_coarse, y, dy)      # g["x"] [n_coarse, F], g["coords"] [E, d]
     p = point_sets_grad(handle, g["coords"]);  p["queries"], p["sources"]
 
-interpolate and interpolate_grad(want=("x",)) take ANY weights [E]: mean pooling and quadrature-weighted transfer are the same calls."""
+interpolate and interpolate_grad(want=("x",)) take ANY weights [E]: mean pooling and quadrature-weighted transfer are the same calls.
+
+And the way down, fine to coarse (athena_amd/csrc/pool.hip): the set-abstraction step -- an MLP on every (sample, neighbour) pair, then
+the maximum over each sample's neighbourhood, with the arg-max that the reverse step needs:
+
+    sample, coarse, sample_offsets, cover = farthest_points(points, offsets, ratio=0.05)
+    handle, coords, eoff = DeviceGraph.from_point_sets_knn(coarse, points, k=16, query_offsets=sample_offsets, source_offsets=offsets)
+    ... the edge MLP on (coords, the neighbours' features) returns h [E, F]
+    y, arg = pool_max(handle, edges=h)                                  # [n_coarse, F], [n_coarse, F] int32
+    ... the layers above return dy [n_coarse, F]
+    dh = pool_max_grad(handle, arg, dy, to="edges")                     # [E, F]
+
+pool_max(handle, x=...) takes per-vertex values instead (on any handle, square ones too) and pool_max_grad(..., to="x") is its
+reverse."""
 import ctypes as C
 
 import numpy as np
@@ -104,6 +117,16 @@ def _device_f32(t, shape, what):
     ok = isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.dim() == len(shape)
     if not (ok and all(want is None or int(have) == want for have, want in zip(t.shape, shape))):
         raise ValueError(f"{what} must be a contiguous float32 device tensor [{', '.join('*' if s is None else str(s) for s in shape)}]")
+    return t
+
+
+def _device_i32(t, shape, what):
+    """the same for a contiguous int32 device tensor"""
+    import torch
+
+    ok = isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == tuple(shape)
+    if not ok:
+        raise ValueError(f"{what} must be a contiguous int32 device tensor [{', '.join(str(s) for s in shape)}]")
     return t
 
 
@@ -181,6 +204,60 @@ def interpolate_grad(handle, coords, weights, x, y, dy, eps=1e-16, want=("x", "c
         _capi.call("athena_mp_interp_bwd_coords", handle.handle, dim, F, ptr(coords), float(eps), ptr(weights), ptr(x), ptr(y), ptr(dy),
                    ptr(res["coords"]))
     return res
+
+
+def pool_max(handle, x=None, edges=None, want_arg=True, out=None):
+    """The maximum over each row of the handle, and where it was found (athena_mp_pool_max_fwd, athena_mp_pool_max_edges_fwd; the
+    definition is in include/athena_mp.h).  Exactly one of x [n_cols, F] (per-vertex values, any handle) and edges [E, F] (per-edge
+    values, a handle with one entry per edge column: from_point_sets, from_point_sets_knn) is given: contiguous float32 device
+    tensors.  Returns (y, arg): y [n_rows, F] float32, the bits of the first maximum in CSR order (a NaN wins over every number),
+    +0 along an empty row; arg [n_rows, F] int32, the 0-based column (source) it came from, -1 along an empty row -- None with
+    want_arg=False.  out: a (y, arg) pair of contiguous device tensors to write into (arg: int32, or None)."""
+    import torch
+
+    if (x is None) == (edges is None):
+        raise ValueError("exactly one of x and edges must be given")
+    n = handle.n_rows
+    if x is not None:
+        v, entry = _device_f32(x, (handle.n_cols, None), "x"), "athena_mp_pool_max_fwd"
+    else:
+        v, entry = _device_f32(edges, (handle.n_edge_cols, None), "edges"), "athena_mp_pool_max_edges_fwd"
+    F = int(v.shape[1])
+    y, arg = (None, None) if out is None else out
+    if y is None:
+        y = torch.empty((n, F), dtype=torch.float32, device=v.device)
+    y = _device_f32(y, (n, F), "out[0]")
+    if arg is None and want_arg:
+        arg = torch.empty((n, F), dtype=torch.int32, device=v.device)
+    if arg is not None:
+        arg = _device_i32(arg, (n, F), "out[1]")
+    _capi.use_torch_stream()
+    _capi.call(entry, handle.handle, F, C.c_void_p(v.data_ptr()), C.c_void_p(y.data_ptr()),
+               C.c_void_p(arg.data_ptr()) if arg is not None else None)
+    return y, arg
+
+
+def pool_max_grad(handle, arg, dy, to="x", out=None):
+    """The reverse of pool_max (athena_mp_pool_max_bwd_x, athena_mp_pool_max_bwd_edges): arg [n_rows, F] int32 as pool_max returned
+    it and dy [n_rows, F] float32 on the device.  to="x": dx [n_cols, F], row j = the sum of dy[i] over the rows i that chose j,
+    ascending, bit for bit the sequential fp32 sum; a column nobody chose gets 0.  to="edges": dh [E, F], dh[e] = dy[i] where row i
+    chose the entry of edge e, else 0.  The whole of dy[i, f] goes to the one entry arg names: a tie is not shared.  out: a contiguous
+    float32 device tensor of the result's shape to write into."""
+    import torch
+
+    if to not in ("x", "edges"):
+        raise ValueError('to must be "x" or "edges"')
+    dy = _device_f32(dy, (handle.n_rows, None), "dy")
+    F = int(dy.shape[1])
+    arg = _device_i32(arg, (handle.n_rows, F), "arg")
+    shape = (handle.n_cols if to == "x" else handle.n_edge_cols, F)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=dy.device)
+    out = _device_f32(out, shape, "out")
+    _capi.use_torch_stream()
+    _capi.call("athena_mp_pool_max_bwd_x" if to == "x" else "athena_mp_pool_max_bwd_edges", handle.handle, F, C.c_void_p(arg.data_ptr()),
+               C.c_void_p(dy.data_ptr()), C.c_void_p(out.data_ptr()))
+    return out
 
 
 def farthest_points(points, offsets=None, n_samples=None, ratio=None, start=None, want_sqdist=False, device=0):

@@ -463,6 +463,41 @@ int athena_mp_interp_host(const athena_mp_graph *g, int32_t dim, int32_t F, cons
                           float *weights);
 int athena_mp_interp_bwd_host(const athena_mp_graph *g, int32_t dim, int32_t F, const float *coords, float eps, const float *x,
                               const float *dy, float *dx, float *dcoords);
+/* Max pooling over a handle's rows, with its arg-max and both reverse steps (pool.hip): the maximum over each neighbourhood -- the
+ * reduction of PointNet++'s set abstraction (an MLP on every (sample, neighbour) pair, then the maximum over the neighbours), of
+ * EdgeConv / DGCNN and of GraphSAGE-pool.  Nothing in the reference corresponds to them.
+ * Definition.  g is any handle.  Row i is its forward CSR as athena_mp_graph_export shows it (rowptr, col, eid), column j its
+ * transposed CSR (t_rowptr, t_src, t_eid; rows ascending).  Values are fp32.  Nothing is computed on them: they are compared and
+ * copied.  Arrays are row-major.
+ *   Vertex form (athena_mp_pool_max_fwd), x [n_cols, F] -> y [n_rows, F] and arg [n_rows, F] int32:
+ *     for k = rowptr[i] .. rowptr[i+1]-1 in order, v = x[col[k], f]: entry k replaces the best so far when there is none yet, or
+ *     v > best, or v is a NaN and best is not.  So the first maximum in row order wins; of +0 and -0, whichever comes first stays; a
+ *     NaN wins over every number, and the first NaN stays.  y[i, f] is the bits of the chosen value, arg[i, f] its col[k], 0-based.
+ *     An empty row gives y = +0 and arg = -1.  arg may be NULL.
+ *   Edge form (athena_mp_pool_max_edges_fwd), h [E, F] -> y, arg: the same walk with v = h[eid[k], f]; arg is again col[k].
+ *   Reverse of the vertex form (athena_mp_pool_max_bwd_x), arg, dy [n_rows, F] -> dx [n_cols, F]:
+ *     acc = +0; for k = t_rowptr[j] .. t_rowptr[j+1]-1 in order, with i = t_src[k]: where arg[i, f] == j, acc = acc + dy[i, f]; other
+ *     entries add nothing.  dx[j, f] = acc: a sequential fp32 sum over the rows ascending, bit-defined.
+ *   Reverse of the edge form (athena_mp_pool_max_bwd_edges), arg, dy -> dh [E, F]:
+ *     for the entry k of row i with e = eid[k], j = col[k]: dh[e, f] = dy[i, f] where arg[i, f] == j, else +0.
+ *   Every element of every output is written.  There are no atomics: two runs are byte-identical.
+ * Precondition, not checked: no row holds the same column twice -- every builder of the library guarantees this; with a repeated
+ * column arg names both entries and the reverse steps count dy once for each.
+ * The edge forms need what the interpolation entries need: edge columns, an edge id on every entry, and exactly as many entries as
+ * edge columns (athena_mp_graph_create_bipartite_dev builds exactly that); each dh[e, :] then has one writer.  The vertex forms take
+ * square handles too: one-set radius and k-nearest-neighbour graphs, and handles without edge ids.
+ * Refused with a message: for the edge forms a handle without edge columns, an entry that carries no edge id, more or fewer entries
+ * than edge columns; F < 1.  The library stays usable after a refusal.  E = 0, n_rows = 0 and n_cols = 0 succeed (empty arrays may
+ * be NULL).  A caller's pointer needs only 4-byte alignment. */
+int athena_mp_pool_max_fwd(const athena_mp_graph *g, int32_t F, const float *x_dev, float *y_dev, int32_t *arg_dev);
+int athena_mp_pool_max_edges_fwd(const athena_mp_graph *g, int32_t F, const float *h_dev, float *y_dev, int32_t *arg_dev);
+int athena_mp_pool_max_bwd_x(const athena_mp_graph *g, int32_t F, const int32_t *arg_dev, const float *dy_dev, float *dx_dev);
+int athena_mp_pool_max_bwd_edges(const athena_mp_graph *g, int32_t F, const int32_t *arg_dev, const float *dy_dev, float *dh_dev);
+/* The same for callers that hold Fortran arrays, staged through HBM.  athena_mp_pool_max_host: exactly one of x [n_cols, F] (the
+ * vertex form) and h [E, F] (the edge form) is not NULL; arg [n_rows, F] may be NULL.  athena_mp_pool_max_bwd_host: dx [n_cols, F], the
+ * reverse of the vertex form, and dh [E, F], the reverse of the edge form, both from the one arg; each may be NULL, not both. */
+int athena_mp_pool_max_host(const athena_mp_graph *g, int32_t F, const float *x, const float *h, float *y, int32_t *arg);
+int athena_mp_pool_max_bwd_host(const athena_mp_graph *g, int32_t F, const int32_t *arg, const float *dy, float *dx, float *dh);
 /* athena_mp_edge_grad_to_points and athena_mp_periodic_grad with every array on the host (a handle plus Fortran arrays), staged
  * through HBM */
 int athena_mp_edge_grad_to_points_host(const athena_mp_graph *g, int32_t dim, const float *dcoords, float *dpoints);
