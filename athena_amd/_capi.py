@@ -79,6 +79,10 @@ _PROTOS = {
     "athena_mp_pool_max_bwd_edges": [_vp, _i32, _vp, _vp, _vp],
     "athena_mp_pool_max_host": [_vp, _i32, _vp, _vp, _vp, _vp],
     "athena_mp_pool_max_bwd_host": [_vp, _i32, _vp, _vp, _vp, _vp],
+    "athena_mp_edge_gather_fwd": [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _vp],
+    "athena_mp_edge_gather_bwd": [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp],
+    "athena_mp_edge_gather_host": [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _vp],
+    "athena_mp_edge_gather_bwd_host": [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp],
     "athena_mp_graph_export": [_vp, _i32, _vp, _i64, _vp],
     "athena_mp_graph_destroy": [_vp],
     "athena_mp_graph_key": [_i32, _i64, _vp, _vp, C.POINTER(C.c_uint64)],

@@ -207,6 +207,8 @@ int periodic_grad_check(const athena_mp_graph *g, int32_t B, int32_t n, const in
 int interp_check(const char *who, const athena_mp_graph *g, const int32_t *dim, const int32_t *F, const float *eps);
 // argument checks of the max-pooling entries (pool.hip), shared with their *_host forms; the edge forms add interp_check's conditions
 int pool_check(const char *who, const athena_mp_graph *g, int32_t F, bool edge_form);
+// argument checks of the edge-gather entries (edge_gather.hip), shared with their *_host forms: interp_check on the handle, then the widths
+int edge_gather_check(const char *who, const athena_mp_graph *g, int32_t Fs, int32_t Fq, int32_t dim, int32_t relative, int32_t ld);
 void graph_cache_clear(); // idle and live handles of athena_mp_graph_acquire (capi.hip)
 void host_pool_release();   // staging buffers of the *_host entry points (host.hip)
 uint64_t content_hash(const void *p, size_t bytes);   // every byte of a host array (capi.hip)

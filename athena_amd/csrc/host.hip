@@ -732,6 +732,36 @@ int athena_mp_pool_max_bwd_host(const athena_mp_graph *g, int32_t F, const int32
                       return dh ? athena_mp_pool_max_bwd_edges(g, F, (int32_t *)p[0], (float *)p[1], (float *)p[3]) : 0;
                   });
 }
+// ---- the edge MLP's input (edge_gather.hip): h goes up as well as down, so that its pad columns keep the caller's words ------------
+int athena_mp_edge_gather_host(const athena_mp_graph *g, int32_t Fs, const float *xs, int32_t Fq, const float *xq, int32_t dim,
+                               const float *coords, int32_t relative, int32_t ld, float *h)
+{
+    if (int rc = edge_gather_check("edge_gather_host", g, Fs, Fq, dim, relative, ld)) return rc;
+    AMP_REQUIRE((Fs == 0 || g->n_cols == 0 || xs) && (Fq == 0 || g->n_rows == 0 || xq) && (dim == 0 || g->nnz == 0 || coords) &&
+                    (g->nnz == 0 || h),
+                "edge_gather_host: null array");
+    return staged({{xs, nullptr, xs ? fb(g->n_cols, Fs) : 0}, {xq, nullptr, xq ? fb(g->n_rows, Fq) : 0},
+                   {coords, nullptr, coords ? fb(g->n_edge_cols, dim) : 0}, {h, h, h ? fb(g->n_edge_cols, ld) : 0}},
+                  [&](std::vector<void *> &p) {
+                      return athena_mp_edge_gather_fwd(g, Fs, xs ? (float *)p[0] : nullptr, Fq, xq ? (float *)p[1] : nullptr, dim,
+                                                       coords ? (float *)p[2] : nullptr, relative, ld, h ? (float *)p[3] : nullptr);
+                  });
+}
+int athena_mp_edge_gather_bwd_host(const athena_mp_graph *g, int32_t Fs, int32_t Fq, int32_t dim, int32_t relative, int32_t ld,
+                                   const float *dh, float *dxs, float *dxq, float *dcoords)
+{
+    AMP_REQUIRE(dxs || dxq || dcoords, "edge_gather_bwd_host: dxs, dxq and dcoords are all null: nothing to compute");
+    if (int rc = edge_gather_check("edge_gather_bwd_host", g, Fs, Fq, dim, relative, ld)) return rc;
+    AMP_REQUIRE(g->nnz == 0 || dh, "edge_gather_bwd_host: null array");
+    auto out = [](float *host, size_t bytes) { return Stage{nullptr, host, host ? bytes : 0, true}; };
+    return staged({{dh, nullptr, dh ? fb(g->n_edge_cols, ld) : 0}, out(dxs, fb(g->n_cols, Fs)), out(dxq, fb(g->n_rows, Fq)),
+                   out(dcoords, fb(g->n_edge_cols, dim))},
+                  [&](std::vector<void *> &p) {
+                      return athena_mp_edge_gather_bwd(g, Fs, Fq, dim, relative, ld, dh ? (float *)p[0] : nullptr,
+                                                       dxs ? (float *)p[1] : nullptr, dxq ? (float *)p[2] : nullptr,
+                                                       dcoords ? (float *)p[3] : nullptr);
+                  });
+}
 int athena_mp_periodic_grad_host(const athena_mp_graph *g, int32_t B, int32_t n, const int32_t *offsets, const int64_t *edge_offsets,
                                  const float *lat, float cutoff_max, const float *vec, const float *dfeature, int32_t fe_cols,
                                  const float *dvec, float *dcart, float *dfrac, float *virial, float *dlat)

@@ -61,6 +61,7 @@ module athena_mp_c
   public :: athena_mp_interp_host, athena_mp_interp_bwd_host
   public :: athena_mp_pool_max_fwd, athena_mp_pool_max_edges_fwd, athena_mp_pool_max_bwd_x, athena_mp_pool_max_bwd_edges
   public :: athena_mp_pool_max_host, athena_mp_pool_max_bwd_host
+  public :: athena_mp_edge_gather_fwd, athena_mp_edge_gather_bwd, athena_mp_edge_gather_host, athena_mp_edge_gather_bwd_host
   public :: athena_mp_periodic_pairs, athena_mp_periodic_graph_host, athena_mp_periodic_stats
   public :: athena_mp_edge_grad_to_points, athena_mp_periodic_grad
   public :: athena_mp_edge_grad_to_points_host, athena_mp_periodic_grad_host
@@ -866,6 +867,38 @@ module athena_mp_c
        integer(c_int32_t), value :: F
        integer(c_int32_t), intent(in) :: arg(F, *)
        real(c_float), intent(in) :: dy(F, *)
+     end function
+     !! the edge MLP's input over a two-set handle (definition: include/athena_mp.h): h (ld, E), column e = xs(:, j) (relative = 1:
+     !! less xq(:, i)), then xq(:, i), then coords(:, e) for the entry (i, j) of edge e; ld >= Fs + Fq + dim, the elements beyond
+     !! stay as they are; a block of width 0 is c_null_ptr
+     integer(c_int) function athena_mp_edge_gather_fwd(graph, Fs, xs_dev, Fq, xq_dev, dim, coords_dev, relative, ld, h_dev) &
+          bind(C, name="athena_mp_edge_gather_fwd")
+       import :: c_int, c_int32_t, c_ptr
+       type(c_ptr), value :: graph, xs_dev, xq_dev, coords_dev, h_dev
+       integer(c_int32_t), value :: Fs, Fq, dim, relative, ld
+     end function
+     !! its reverse: dh (ld, E) -> dxs (Fs, n_cols), dxq (Fq, n_rows), dcoords (dim, E), each a device pointer or c_null_ptr
+     integer(c_int) function athena_mp_edge_gather_bwd(graph, Fs, Fq, dim, relative, ld, dh_dev, dxs_dev, dxq_dev, dcoords_dev) &
+          bind(C, name="athena_mp_edge_gather_bwd")
+       import :: c_int, c_int32_t, c_ptr
+       type(c_ptr), value :: graph, dh_dev, dxs_dev, dxq_dev, dcoords_dev
+       integer(c_int32_t), value :: Fs, Fq, dim, relative, ld
+     end function
+     !! the same with host arrays (staged): xs, xq, coords are c_loc of the host arrays, c_null_ptr for a block of width 0
+     integer(c_int) function athena_mp_edge_gather_host(graph, Fs, xs, Fq, xq, dim, coords, relative, ld, h) &
+          bind(C, name="athena_mp_edge_gather_host")
+       import :: c_int, c_int32_t, c_float, c_ptr
+       type(c_ptr), value :: graph, xs, xq, coords
+       integer(c_int32_t), value :: Fs, Fq, dim, relative, ld
+       real(c_float), intent(inout) :: h(ld, *)
+     end function
+     !! ... and dh (ld, E) -> dxs, dxq, dcoords: c_loc of the host arrays, or c_null_ptr (not all three)
+     integer(c_int) function athena_mp_edge_gather_bwd_host(graph, Fs, Fq, dim, relative, ld, dh, dxs, dxq, dcoords) &
+          bind(C, name="athena_mp_edge_gather_bwd_host")
+       import :: c_int, c_int32_t, c_float, c_ptr
+       type(c_ptr), value :: graph, dxs, dxq, dcoords
+       integer(c_int32_t), value :: Fs, Fq, dim, relative, ld
+       real(c_float), intent(in) :: dh(ld, *)
      end function
      !! ... dfeature, dvec and the four outputs passed as c_loc of host arrays, or c_null_ptr
      integer(c_int) function athena_mp_periodic_grad_host(graph, n_structures, n_atoms, offsets, edge_offsets, lat, cutoff_max, &

@@ -39,13 +39,17 @@ the maximum over each sample's neighbourhood, with the arg-max that the reverse 
 
     sample, coarse, sample_offsets, cover = farthest_points(points, offsets, ratio=0.05)
     handle, coords, eoff = DeviceGraph.from_point_sets_knn(coarse, points, k=16, query_offsets=sample_offsets, source_offsets=offsets)
-    ... the edge MLP on (coords, the neighbours' features) returns h [E, F]
+    m = edge_features(handle, x_sources=x, coords=coords, pad_to=4)     # [E, F_x + d]: the edge MLP's input (edge_gather.hip)
+    ... the edge MLP on m returns h [E, F]
     y, arg = pool_max(handle, edges=h)                                  # [n_coarse, F], [n_coarse, F] int32
     ... the layers above return dy [n_coarse, F]
     dh = pool_max_grad(handle, arg, dy, to="edges")                     # [E, F]
+    ... the edge MLP's reverse returns dm [E, F_x + d]
+    g = edge_features_grad(handle, dm, widths=(F_x, 0, d))              # g["sources"] [n_points, F_x], g["coords"] [E, d]
+    p = point_sets_grad(handle, g["coords"]);  p["queries"], p["sources"]
 
 pool_max(handle, x=...) takes per-vertex values instead (on any handle, square ones too) and pool_max_grad(..., to="x") is its
-reverse."""
+reverse.  edge_features(..., x_queries=..., relative=True) makes EdgeConv's input (x_j - x_i, x_i)."""
 import ctypes as C
 
 import numpy as np
@@ -258,6 +262,84 @@ def pool_max_grad(handle, arg, dy, to="x", out=None):
     _capi.call("athena_mp_pool_max_bwd_x" if to == "x" else "athena_mp_pool_max_bwd_edges", handle.handle, F, C.c_void_p(arg.data_ptr()),
                C.c_void_p(dy.data_ptr()), C.c_void_p(out.data_ptr()))
     return out
+
+
+def _device_rows(t, rows, cols, what):
+    """t is a float32 device tensor [rows, cols] (cols None: any) whose rows are contiguous and do not overlap -- a contiguous tensor
+    or a view buffer[:, :cols] of one --, or ValueError; returns its row pitch in elements"""
+    import torch
+
+    ok = isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and int(t.shape[0]) == rows
+    ok = ok and (cols is None or int(t.shape[1]) == cols)
+    ok = ok and (t.numel() == 0 or ((t.shape[1] == 1 or t.stride(1) == 1) and (rows == 1 or t.stride(0) >= t.shape[1])))
+    if not ok:
+        raise ValueError(f"{what} must be a float32 device tensor [{rows}, {'*' if cols is None else cols}] with contiguous rows "
+                         "(stride(1) == 1, stride(0) >= the width)")
+    return int(t.shape[1]) if t.numel() == 0 or rows == 1 else int(t.stride(0))
+
+
+def edge_features(handle, x_sources=None, x_queries=None, coords=None, relative=False, pad_to=1, out=None):
+    """The edge MLP's input over a two-set handle (athena_mp_edge_gather_fwd; the definition is in include/athena_mp.h): for the
+    entry of row i and column j with edge id e, h[e] = (x_sources[j], x_queries[i], coords[e]) -- each block present when its
+    tensor is given: x_sources [n_cols, Fs], x_queries [n_rows, Fq], coords [E, dim], contiguous float32 device tensors.
+    relative=True (needs Fs == Fq) makes the first block x_sources[j] - x_queries[i].  Copies keep the bits.  Returns h [E, W],
+    W = Fs + Fq + dim: a view of an [E, ld] buffer, ld = W rounded up to a multiple of pad_to, so torch.matmul(h, Wt) takes it as
+    it is; with ld, Fs and Fq multiples of 4 the rows move 16 bytes at a time (W = 64 + 3: pad_to=4).  The buffer's columns
+    beyond W are never written.  out: a float32 device tensor [E, W] with contiguous rows to write into, its stride(0) the pitch
+    (pad_to is then not used)."""
+    import torch
+
+    E = handle.n_edge_cols
+    given = [t for t in (x_sources, x_queries, coords) if t is not None]
+    if not given:
+        raise ValueError("at least one of x_sources, x_queries and coords must be given")
+    xs = None if x_sources is None else _device_f32(x_sources, (handle.n_cols, None), "x_sources")
+    xq = None if x_queries is None else _device_f32(x_queries, (handle.n_rows, None), "x_queries")
+    co = None if coords is None else _device_f32(coords, (E, None), "coords")
+    Fs, Fq, dim = (0 if t is None else int(t.shape[1]) for t in (xs, xq, co))
+    W = Fs + Fq + dim
+    if out is None:
+        if int(pad_to) < 1:
+            raise ValueError("pad_to must be at least 1")
+        ld = -(-W // int(pad_to)) * int(pad_to)
+        out = torch.empty((E, ld), dtype=torch.float32, device=given[0].device)[:, :W]
+    else:
+        ld = _device_rows(out, E, W, "out")
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.shape[1] > 0 else None
+    _capi.use_torch_stream()
+    _capi.call("athena_mp_edge_gather_fwd", handle.handle, Fs, ptr(xs), Fq, ptr(xq), dim, ptr(co), int(bool(relative)), max(ld, W),
+               C.c_void_p(out.data_ptr()))
+    return out
+
+
+def edge_features_grad(handle, dh, widths, relative=False, want=("sources", "queries", "coords"), out=None):
+    """The reverse of edge_features (athena_mp_edge_gather_bwd): dh [E, W] float32 on the device, the gradient with respect to h --
+    contiguous, or a view with contiguous rows (stride(1) == 1, stride(0) >= W), as edge_features returns one --, and widths =
+    (Fs, Fq, dim), W = Fs + Fq + dim.  Returns a dict of device tensors for the names in `want`: "sources" [n_cols, Fs], row j =
+    the sum of dh[e, :Fs] over the handle's column j, queries ascending; "queries" [n_rows, Fq], row i = the sum of
+    dh[e, Fs:Fs + Fq] over row i in CSR order, with relative each entry's dh[e, :Fs] subtracted after it; "coords" [E, dim], a copy
+    of dh's last block, what point_sets_grad takes.  Bit for bit the sequential fp32 sums; no atomics.  out: a dict of contiguous
+    float32 device tensors to write into, by the same names."""
+    import torch
+
+    Fs, Fq, dim = (int(w) for w in widths)
+    E = handle.n_edge_cols
+    ld = _device_rows(dh, E, Fs + Fq + dim, "dh")
+    want = tuple(want)
+    if not want or any(w not in ("sources", "queries", "coords") for w in want):
+        raise ValueError('want must name some of ("sources", "queries", "coords")')
+    shapes = {"sources": (handle.n_cols, Fs), "queries": (handle.n_rows, Fq), "coords": (E, dim)}
+    res = {}
+    for w in want:
+        t = None if out is None else out.get(w)
+        if t is None:
+            t = torch.empty(shapes[w], dtype=torch.float32, device=dh.device)
+        res[w] = _device_f32(t, shapes[w], f"out[{w!r}]")
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.shape[1] > 0 else None
+    _capi.use_torch_stream()
+    _capi.call("athena_mp_edge_gather_bwd", handle.handle, Fs, Fq, dim, int(bool(relative)), max(ld, Fs + Fq + dim),
+               C.c_void_p(dh.data_ptr()), ptr(res.get("sources")), ptr(res.get("queries")), ptr(res.get("coords")))
+    return res
 
 
 def farthest_points(points, offsets=None, n_samples=None, ratio=None, start=None, want_sqdist=False, device=0):

@@ -498,6 +498,54 @@ int athena_mp_pool_max_bwd_edges(const athena_mp_graph *g, int32_t F, const int3
  * reverse of the vertex form, and dh [E, F], the reverse of the edge form, both from the one arg; each may be NULL, not both. */
 int athena_mp_pool_max_host(const athena_mp_graph *g, int32_t F, const float *x, const float *h, float *y, int32_t *arg);
 int athena_mp_pool_max_bwd_host(const athena_mp_graph *g, int32_t F, const int32_t *arg, const float *dy, float *dx, float *dh);
+/* The gather that makes the edge MLP's input over a two-set handle, with its reverse (edge_gather.hip): h[e, :] = (xs[col], xq[row],
+ * coords[e]) for every entry, the step between athena_mp_knn_pairs_bipartite and the MLP of PointNet++'s set abstraction and of
+ * EdgeConv (relative: the first block is xs[col] - xq[row]), whose output athena_mp_pool_max_edges_fwd reduces; and back from the
+ * MLP's input gradient to both sets' features and to coords.  Nothing in the reference corresponds to them.
+ * Definition.  g is a handle that the edge forms of interp and pool accept:
+ *   - it has edge columns;
+ *   - every entry has an edge id;
+ *   - it has as many entries as edge columns.
+ * Row i is the forward CSR rowptr, col, eid.  Column j is the transposed CSR t_rowptr, t_src, t_eid, rows ascending.  All values are
+ * fp32.  Arrays are row-major.
+ *   Operands:  xs [n_cols, Fs] source features;  xq [n_rows, Fq] query features;  coords [E, dim] the edge input;  h [E, ld] forward
+ *   output;  dh [E, ld] reverse input.
+ *   - Fs, Fq, dim >= 0 and W = Fs + Fq + dim >= 1.
+ *   - ld >= W is the row pitch of h and dh in elements.
+ *   - relative is 0 or 1.  relative = 1 needs Fs == Fq >= 1.
+ *   - A block of width 0 has a NULL pointer and is skipped.
+ *   Forward.  For the entry k of row i, with j = col[k] and e = eid[k]:
+ *     h[e, f],           f < Fs:   xs[j, f] bit for bit, or with relative the fp32 difference xs[j, f] - xq[i, f]
+ *     h[e, Fs + f],      f < Fq:   xq[i, f] bit for bit
+ *     h[e, Fs + Fq + c], c < dim:  coords[e, c] bit for bit
+ *   - "Bit for bit" means a copy, not an arithmetic operation.  -0, infinities, NaN payloads and signalling NaNs pass unchanged.
+ *   - Every one of the W defined columns of every row is written exactly once.
+ *   - Columns W .. ld - 1 are never written.
+ *   - When the difference is a NaN (a NaN operand, or inf - inf), the definition requires a NaN and leaves its payload open.
+ *   Reverse.  Each of the three outputs is produced when its pointer is non-NULL.
+ *   - dxs[j, f]: acc = +0.  Then for k = t_rowptr[j] .. in order, with e = t_eid[k]: acc = acc + dh[e, f].
+ *   - dxq[i, f]: acc = +0.  Then for k = rowptr[i] .. in order, with e = eid[k]: acc = acc + dh[e, Fs + f], and with relative, after
+ *     that, acc = acc - dh[e, f].
+ *   - dcoords[e, c] = dh[e, Fs + Fq + c] bit for bit.
+ *   The sums are sequential fp32 sums.  Every element of every requested output is written.  Empty rows and columns give +0.  Columns
+ *   W .. ld - 1 of dh are never read.
+ *   The kernels use no atomics.  Two runs are byte-identical.
+ * Empty sets succeed (empty arrays may be NULL).  Pointers need 4-byte alignment only; with Fs % 4 == 0, Fq % 4 == 0, ld % 4 == 0 and
+ * every array on a 16-byte boundary the rows move 16 bytes at a time -- the same bytes, sooner -- so a W that is no multiple of 4 is
+ * worth a padded pitch (W = 64 + 3: ld = 68).
+ * Refused with a message: what athena_mp_interp_fwd refuses of a handle; ld < W; relative with Fs != Fq; relative with Fs = 0; W < 1;
+ * a negative width; a NULL block of positive width; relative outside 0, 1.  The library stays usable after a refusal. */
+int athena_mp_edge_gather_fwd(const athena_mp_graph *g, int32_t Fs, const float *xs_dev, int32_t Fq, const float *xq_dev, int32_t dim,
+                              const float *coords_dev, int32_t relative, int32_t ld, float *h_dev);
+int athena_mp_edge_gather_bwd(const athena_mp_graph *g, int32_t Fs, int32_t Fq, int32_t dim, int32_t relative, int32_t ld,
+                              const float *dh_dev, float *dxs_dev, float *dxq_dev, float *dcoords_dev);
+/* The same for callers that hold Fortran arrays, staged through HBM.  athena_mp_edge_gather_host: h [E, ld] goes up before the call
+ * and comes back after it, so its columns W .. ld - 1 keep what the caller put there.  athena_mp_edge_gather_bwd_host: each of dxs
+ * [n_cols, Fs], dxq [n_rows, Fq] and dcoords [E, dim] may be NULL, not all three. */
+int athena_mp_edge_gather_host(const athena_mp_graph *g, int32_t Fs, const float *xs, int32_t Fq, const float *xq, int32_t dim,
+                               const float *coords, int32_t relative, int32_t ld, float *h);
+int athena_mp_edge_gather_bwd_host(const athena_mp_graph *g, int32_t Fs, int32_t Fq, int32_t dim, int32_t relative, int32_t ld,
+                                   const float *dh, float *dxs, float *dxq, float *dcoords);
 /* athena_mp_edge_grad_to_points and athena_mp_periodic_grad with every array on the host (a handle plus Fortran arrays), staged
  * through HBM */
 int athena_mp_edge_grad_to_points_host(const athena_mp_graph *g, int32_t dim, const float *dcoords, float *dpoints);
