@@ -203,11 +203,15 @@ int points_grad_check(const athena_mp_graph *g, int32_t dim);
 int point_sets_grad_check(const athena_mp_graph *g, int32_t dim, bool want_queries, bool want_sources);
 int periodic_grad_check(const athena_mp_graph *g, int32_t B, int32_t n, const int32_t *offsets, const int64_t *edge_offsets,
                         float cutoff_max, bool has_dfeature, int32_t fe_cols, bool has_dvec);
-// argument checks of the interpolation entries (interp.hip), shared with their *_host forms; dim, F, eps: null where the entry takes none
+// the handle carries one entry per edge column, as athena_mp_graph_create_bipartite_dev builds it (interp.hip): what the
+// interpolation entries, the edge forms of pooling and the edge gather need of it
+int edge_form_check(const char *who, const athena_mp_graph *g);
+// argument checks of the interpolation entries (interp.hip), shared with their *_host forms: edge_form_check, then dim, F, eps
+// (null where the entry takes none)
 int interp_check(const char *who, const athena_mp_graph *g, const int32_t *dim, const int32_t *F, const float *eps);
-// argument checks of the max-pooling entries (pool.hip), shared with their *_host forms; the edge forms add interp_check's conditions
+// argument checks of the max-pooling entries (pool.hip), shared with their *_host forms; the edge forms add edge_form_check
 int pool_check(const char *who, const athena_mp_graph *g, int32_t F, bool edge_form);
-// argument checks of the edge-gather entries (edge_gather.hip), shared with their *_host forms: interp_check on the handle, then the widths
+// argument checks of the edge-gather entries (edge_gather.hip), shared with their *_host forms: edge_form_check, then the widths
 int edge_gather_check(const char *who, const athena_mp_graph *g, int32_t Fs, int32_t Fq, int32_t dim, int32_t relative, int32_t ld);
 void graph_cache_clear(); // idle and live handles of athena_mp_graph_acquire (capi.hip)
 void host_pool_release();   // staging buffers of the *_host entry points (host.hip)

@@ -15,28 +15,24 @@
 //   bwd_coords:  e = (i, j):  g_e = sum_f dy[i, f] * (x[j, f] - y[i, f]) (order free);  t_e = -(weights[e] * w_e) * g_e;
 //                dcoords[e, c] = (2 d_c) * t_e;  exactly +0 where s_e <= eps (the clamp) or w_e = 0.
 //
-// How.  interp_gather_kernel is the hot launch, one template for fwd and bwd_x: G lanes share a row, G the smallest power of two from
-// 4 with 4 G >= F (a full wave from F = 193; more columns than 256 take further passes), so no lane idles at F = 16, 64, 128, 256.
-// The group's lanes load the column id and the weight of G entries, one entry per lane; the entries then pass through the group in
-// entry order (__shfl, no LDS) while every lane adds its own four feature columns: the sequential sum, bit for bit, whatever the row
-// length -- a hub row of a radius handle takes more rounds.  The feature loads carry no branch (a lane past its row's end reads row
-// 0 and selects its old sum), so the four entries of an unrolled step are in flight together.  A lane owns columns 4 sub .. 4 sub + 3
-// and moves them 16 bytes at a time when F % 4 == 0 and both arrays start on a 16-byte boundary; otherwise columns sub + G a, four
-// bytes at a time: each column's sum is the same sequence of operations on either route.  No LDS, no atomics, no scratch.
-// interp_weights_kernel: eight lanes per row, the geo_vertex_gather scheme with w_e formed where it is used.
+// How.  The lane groups of row_groups.h.  interp_gather_kernel is the hot launch, one template for fwd and bwd_x: the group's lanes
+// load the column id and the weight of G entries, and every lane adds its own four feature columns in entry order: the sequential
+// sum, bit for bit, the same sequence of operations on either load route (a lane past its row's end selects its old sum).
+// interp_weights_kernel: eight lanes per row, w_e formed where it is used, the row sum in entry order through the group.
 // interp_bwd_coords_kernel: the same groups over the rows, y[i] and dy[i] held in registers; each entry's dot over f is per-lane
 // partials over four adjacent columns (16 bytes a load on the same condition) folded by a fixed __shfl_xor tree, and the lane that
-// loaded an entry finishes its edge.
+// loaded an entry finishes its edge.  It keeps the row set-up and its columns written out, and the gather its columns: through
+// the helpers of row_groups.h their register counts moved (profiles/row_groups_isa.txt).
 // One entry per edge column is what all of this rests on (athena_mp_graph_create_bipartite_dev builds exactly that): every
 // weights[e] and dcoords[e, :] then has one writer.
 #include <math.h>
 
 #include "common.h"
+#include "row_groups.h"
 
 namespace {
 
 constexpr int kWeightGroup = 8;                 // lanes that share a row of the weights kernel
-constexpr int kWeightRows = 256 / kWeightGroup;
 
 // d = coords[e, :] (absent components 0) and s_e
 __device__ __forceinline__ float interp_sqdist(const float *__restrict__ coords, int64_t e, int32_t dim, float &d0, float &d1, float &d2)
@@ -60,32 +56,22 @@ __global__ __launch_bounds__(256) void interp_weights_kernel(int32_t n, const in
                                                              float *__restrict__ weights, float *__restrict__ wsum)
 {
     constexpr int G = kWeightGroup;
-    const int lane = threadIdx.x & 63;
-    const int sub = lane & (G - 1), first = lane & ~(G - 1);
-    const int64_t row = (int64_t)blockIdx.x * kWeightRows + threadIdx.x / G;
-    int32_t beg = 0, len = 0;
-    if (row < n) {
-        beg = rowptr[row];
-        len = rowptr[row + 1] - beg;
-    }
-    int32_t rounds = len;                                           // the longest row of the wave: every lane takes part in every round
-#pragma unroll
-    for (int o = 32; o >= G; o >>= 1) rounds = max(rounds, __shfl_xor(rounds, o));
+    const amp::RowGroup<G> rg(n, rowptr);
     float W = 0.f, w_first = 0.f;
-    for (int32_t k0 = 0; k0 < rounds; k0 += G) {
+    for (int32_t k0 = 0; k0 < rg.longest; k0 += G) {                // the per-lane bound: with rg.rounds this kernel's registers move
         float w = 0.f;
-        if (k0 + sub < len) w = interp_raw_weight(coords, eid[(int64_t)beg + k0 + sub], dim, eps);
+        if (k0 + rg.sub < rg.len) w = interp_raw_weight(coords, eid[(int64_t)rg.beg + k0 + rg.sub], dim, eps);
         if (k0 == 0) w_first = w;
 #pragma unroll
         for (int j = 0; j < G; ++j) {                               // entry order: k0, k0 + 1, ...
-            const float s = __shfl(w, first + j);
-            if (k0 + j < len) W = W + s;
+            const float s = __shfl(w, rg.first + j);
+            if (k0 + j < rg.len) W = W + s;
         }
     }
-    if (row >= n) return;
-    if (wsum && sub == 0) wsum[row] = W;
-    for (int32_t k = sub; k < len; k += G) {
-        const int64_t e = eid[(int64_t)beg + k];
+    if (rg.row >= n) return;
+    if (wsum && rg.sub == 0) wsum[rg.row] = W;
+    for (int32_t k = rg.sub; k < rg.len; k += G) {
+        const int64_t e = eid[(int64_t)rg.beg + k];
         const float w = k < G ? w_first : interp_raw_weight(coords, e, dim, eps);
         weights[e] = W == 0.f ? 0.f : w / W;
     }
@@ -97,40 +83,28 @@ __global__ __launch_bounds__(256) void interp_gather_kernel(int32_t n, const int
                                                             const int32_t *__restrict__ eid, const float *__restrict__ weights,
                                                             const float *__restrict__ x, float *__restrict__ out, int32_t F)
 {
-    constexpr int kRows = 256 / G;
-    const int lane = threadIdx.x & 63;
-    const int sub = lane & (G - 1), first = lane & ~(G - 1);
-    const int64_t row = (int64_t)blockIdx.x * kRows + threadIdx.x / G;
-    int32_t beg = 0, len = 0;
-    if (row < n) {
-        beg = rowptr[row];
-        len = rowptr[row + 1] - beg;
-    }
-    int32_t rounds = len;
-#pragma unroll
-    for (int o = 32; o >= G; o >>= 1) rounds = max(rounds, __shfl_xor(rounds, o));
-    rounds = __builtin_amdgcn_readfirstlane(rounds);               // the same in every lane: a scalar loop bound
+    const amp::RowGroup<G> rg(n, rowptr);
     for (int32_t f0 = 0; f0 < F; f0 += 4 * G) {
-        // this lane's columns, and where it reads them: a column past F reads the last valid place and is never stored
+        // written out: through LaneColumns this kernel's register allocation moves (profiles/row_groups_isa.txt)
         int32_t colv[4];
 #pragma unroll
-        for (int a = 0; a < 4; ++a) colv[a] = VEC ? f0 + 4 * sub + a : f0 + sub + G * a;
+        for (int a = 0; a < 4; ++a) colv[a] = VEC ? f0 + 4 * rg.sub + a : f0 + rg.sub + G * a;
         const int32_t at4 = min(colv[0], F - 4);                    // VEC only: F >= 4 there
         float acc[4] = {0.f, 0.f, 0.f, 0.f};
-        for (int32_t k0 = 0; k0 < rounds; k0 += G) {
+        for (int32_t k0 = 0; k0 < rg.rounds; k0 += G) {
             int32_t c = 0;
             float w = 0.f;
-            if (k0 + sub < len) {
-                const int64_t k = (int64_t)beg + k0 + sub;
+            if (k0 + rg.sub < rg.len) {
+                const int64_t k = (int64_t)rg.beg + k0 + rg.sub;
                 c = idx[k];
                 w = weights[eid[k]];
             }
-            const int nj = min(G, rounds - k0);
+            const int nj = min(G, rg.rounds - k0);
             for (int j0 = 0; j0 < nj; j0 += 4)                      // four entries a step (G is a multiple of 4): their loads fly together
 #pragma unroll
             for (int j = j0; j < j0 + 4; ++j) {                     // entry order: k0, k0 + 1, ...
-                const int32_t cj = __shfl(c, first + j);
-                const float wj = __shfl(w, first + j);
+                const int32_t cj = __shfl(c, rg.first + j);
+                const float wj = __shfl(w, rg.first + j);
                 const float *src = x + (int64_t)cj * F;
                 float v[4];
                 if (VEC) {
@@ -140,7 +114,7 @@ __global__ __launch_bounds__(256) void interp_gather_kernel(int32_t n, const int
 #pragma unroll
                     for (int a = 0; a < 4; ++a) v[a] = src[min(colv[a], F - 1)];
                 }
-                const bool use = k0 + j < len;
+                const bool use = k0 + j < rg.len;
 #pragma unroll
                 for (int a = 0; a < 4; ++a) {
                     const float sum = acc[a] + wj * v[a];
@@ -148,8 +122,8 @@ __global__ __launch_bounds__(256) void interp_gather_kernel(int32_t n, const int
                 }
             }
         }
-        if (row < n) {
-            float *dst = out + row * F;
+        if (rg.row < n) {
+            float *dst = out + rg.row * F;
             if (VEC) {
                 if (colv[0] < F) *reinterpret_cast<float4 *>(dst + colv[0]) = make_float4(acc[0], acc[1], acc[2], acc[3]);
             } else {
@@ -256,37 +230,16 @@ __global__ __launch_bounds__(256) void interp_bwd_coords_kernel(int32_t n, const
     }
 }
 
-// the smallest power of two from 4 with 4 G >= F, at most a wave
-int group_width(int32_t F)
-{
-    int G = 4;
-    while (G < 64 && 4 * G < F) G *= 2;
-    return G;
-}
-
-template <bool VEC>
-void launch_gather(int G, int32_t n, const int32_t *rowptr, const int32_t *idx, const int32_t *eid, const float *weights, const float *x,
-                   float *out, int32_t F)
-{
-    const dim3 grid((unsigned)(((int64_t)n + 256 / G - 1) / (256 / G))), block(256);
-    hipStream_t st = amp::stream();
-    switch (G) {
-    case 4: hipLaunchKernelGGL((interp_gather_kernel<4, VEC>), grid, block, 0, st, n, rowptr, idx, eid, weights, x, out, F); break;
-    case 8: hipLaunchKernelGGL((interp_gather_kernel<8, VEC>), grid, block, 0, st, n, rowptr, idx, eid, weights, x, out, F); break;
-    case 16: hipLaunchKernelGGL((interp_gather_kernel<16, VEC>), grid, block, 0, st, n, rowptr, idx, eid, weights, x, out, F); break;
-    case 32: hipLaunchKernelGGL((interp_gather_kernel<32, VEC>), grid, block, 0, st, n, rowptr, idx, eid, weights, x, out, F); break;
-    default: hipLaunchKernelGGL((interp_gather_kernel<64, VEC>), grid, block, 0, st, n, rowptr, idx, eid, weights, x, out, F); break;
-    }
-}
-
 // out [n, F] over one CSR of the handle; the 16-byte route needs whole float4 columns and both arrays on a 16-byte boundary
 int weighted_gather(int32_t n, const int32_t *rowptr, const int32_t *idx, const int32_t *eid, const float *weights, const float *x,
                     float *out, int32_t F)
 {
     if (n == 0) return 0;
-    const int G = group_width(F);
-    if (F % 4 == 0 && amp::aligned16(x, out)) launch_gather<true>(G, n, rowptr, idx, eid, weights, x, out, F);
-    else launch_gather<false>(G, n, rowptr, idx, eid, weights, x, out, F);
+    const int G = amp::group_width(F);
+    amp::dispatch_group(G, F % 4 == 0 && amp::aligned16(x, out), [&](auto g, auto v) {
+        hipLaunchKernelGGL((interp_gather_kernel<g(), v()>), amp::group_grid(n, G), dim3(256), 0, amp::stream(), n, rowptr, idx, eid, weights,
+                           x, out, F);
+    });
     AMP_LAUNCH_CHECK();
     return 0;
 }
@@ -295,7 +248,7 @@ int weighted_gather(int32_t n, const int32_t *rowptr, const int32_t *idx, const 
 
 namespace amp {
 
-int interp_check(const char *who, const athena_mp_graph *g, const int32_t *dim, const int32_t *F, const float *eps)
+int edge_form_check(const char *who, const athena_mp_graph *g)
 {
     AMP_REQUIRE(g != nullptr, "%s: null graph handle", who);
     AMP_REQUIRE(!(g->n_edge_cols == 0 && g->nnz > 0),
@@ -304,6 +257,12 @@ int interp_check(const char *who, const athena_mp_graph *g, const int32_t *dim, 
                 (long long)(g->nnz - g->n_with_edge), (long long)g->nnz);
     AMP_REQUIRE(g->nnz == (int64_t)g->n_edge_cols, "%s: %lld entries over %d edge columns: need one entry per edge column, as athena_mp_graph_create_bipartite_dev builds it",
                 who, (long long)g->nnz, g->n_edge_cols);
+    return 0;
+}
+
+int interp_check(const char *who, const athena_mp_graph *g, const int32_t *dim, const int32_t *F, const float *eps)
+{
+    if (int rc = edge_form_check(who, g)) return rc;
     AMP_REQUIRE(dim == nullptr || (*dim >= 1 && *dim <= 3), "%s: dim = %d is outside 1..3", who, dim ? *dim : 0);
     AMP_REQUIRE(F == nullptr || *F >= 1, "%s: F = %d: need at least one feature column", who, F ? *F : 0);
     AMP_REQUIRE(eps == nullptr || (isfinite(*eps) && *eps >= 0x1p-60f), "%s: eps = %g: need a finite value of at least 2^-60", who,
@@ -319,9 +278,8 @@ extern "C" int athena_mp_interp_weights(const athena_mp_graph *g, int32_t dim, c
     if (int rc = amp::interp_check("interp_weights", g, &dim, nullptr, &eps)) return rc;
     AMP_REQUIRE(g->n_edge_cols == 0 || (coords_dev != nullptr && weights_dev != nullptr), "interp_weights: null array");
     if (g->n_rows == 0) return 0;
-    hipLaunchKernelGGL(interp_weights_kernel, dim3((unsigned)(((int64_t)g->n_rows + kWeightRows - 1) / kWeightRows)), dim3(256), 0,
-                       amp::stream(), g->n_rows, (const int32_t *)g->rowptr, (const int32_t *)g->eid, dim, coords_dev, eps, weights_dev,
-                       wsum_dev);
+    hipLaunchKernelGGL(interp_weights_kernel, amp::group_grid(g->n_rows, kWeightGroup), dim3(256), 0, amp::stream(), g->n_rows,
+                       (const int32_t *)g->rowptr, (const int32_t *)g->eid, dim, coords_dev, eps, weights_dev, wsum_dev);
     AMP_LAUNCH_CHECK();
     return 0;
 }
@@ -349,29 +307,12 @@ extern "C" int athena_mp_interp_bwd_coords(const athena_mp_graph *g, int32_t dim
     if (int rc = amp::interp_check("interp_bwd_coords", g, &dim, &F, &eps)) return rc;
     if (g->n_edge_cols == 0) return 0;
     AMP_REQUIRE(coords_dev && weights_dev && x_dev && y_dev && dy_dev && dcoords_dev, "interp_bwd_coords: null array");
-    const int G = group_width(F);
-    const dim3 grid((unsigned)(((int64_t)g->n_rows + 256 / G - 1) / (256 / G))), block(256);
-    hipStream_t st = amp::stream();
-    const bool vec = F % 4 == 0 && amp::aligned16(x_dev, y_dev, dy_dev);
-#define ATHENA_INTERP_BWD_COORDS(W)                                                                                                  \
-    do {                                                                                                                             \
-        if (vec)                                                                                                                     \
-            hipLaunchKernelGGL((interp_bwd_coords_kernel<W, true>), grid, block, 0, st, g->n_rows, (const int32_t *)g->rowptr,       \
-                               (const int32_t *)g->col, (const int32_t *)g->eid, dim, F, coords_dev, eps, weights_dev, x_dev, y_dev, \
-                               dy_dev, dcoords_dev);                                                                                 \
-        else                                                                                                                         \
-            hipLaunchKernelGGL((interp_bwd_coords_kernel<W, false>), grid, block, 0, st, g->n_rows, (const int32_t *)g->rowptr,      \
-                               (const int32_t *)g->col, (const int32_t *)g->eid, dim, F, coords_dev, eps, weights_dev, x_dev, y_dev, \
-                               dy_dev, dcoords_dev);                                                                                 \
-    } while (0)
-    switch (G) {
-    case 4: ATHENA_INTERP_BWD_COORDS(4); break;
-    case 8: ATHENA_INTERP_BWD_COORDS(8); break;
-    case 16: ATHENA_INTERP_BWD_COORDS(16); break;
-    case 32: ATHENA_INTERP_BWD_COORDS(32); break;
-    default: ATHENA_INTERP_BWD_COORDS(64); break;
-    }
-#undef ATHENA_INTERP_BWD_COORDS
+    const int G = amp::group_width(F);
+    amp::dispatch_group(G, F % 4 == 0 && amp::aligned16(x_dev, y_dev, dy_dev), [&](auto gw, auto v) {
+        hipLaunchKernelGGL((interp_bwd_coords_kernel<gw(), v()>), amp::group_grid(g->n_rows, G), dim3(256), 0, amp::stream(), g->n_rows,
+                           (const int32_t *)g->rowptr, (const int32_t *)g->col, (const int32_t *)g->eid, dim, F, coords_dev, eps,
+                           weights_dev, x_dev, y_dev, dy_dev, dcoords_dev);
+    });
     AMP_LAUNCH_CHECK();
     return 0;
 }

@@ -12,28 +12,16 @@
 //   bwd_x:      dx[j, f] = acc, acc = +0, then for k = t_rowptr[j] .. in order, i = t_src[k]: acc = acc + dy[i, f] where arg[i, f] == j
 //   bwd_edges:  the entry k of row i, e = eid[k], j = col[k]: dh[e, f] = dy[i, f] where arg[i, f] == j, else +0
 //
-// How.  The lane groups of interp_gather_kernel: G lanes share a row, G the smallest power of two from 4 with 4 G >= F (a full wave from
-// F = 193; more columns than 256 take further passes).  The group's lanes load the ids of G entries, one entry per lane; the entries then
-// pass through the group in entry order (__shfl, no LDS) while every lane keeps the best value and its column for its own four feature
+// How.  The lane groups of row_groups.h.  pool_fwd_kernel: every lane keeps the best value and its column for its own four feature
 // columns: a compare and two selects per column, the chosen value's bits untouched (a select, not a max instruction, which would quiet a
-// signalling NaN and may pick either zero).  The row loads carry no branch (a lane past its row's end reads row 0 and keeps what it
-// has), so the four entries of an unrolled step are in flight together; the wave's longest row is a scalar loop bound.  A lane owns
-// columns 4 sub .. 4 sub + 3 and moves them 16 bytes at a time when F % 4 == 0 and every array of the call starts on a 16-byte boundary
-// (the arg rows too); otherwise columns sub + G a, four bytes at a time: each column sees the same entries in the same order on either
-// route.  pool_bwd_x_kernel: the same groups over the transposed CSR, each entry loading the group's slice of arg[i] and dy[i].
-// pool_bwd_edges_kernel: the groups over the rows with the slices of arg[i] and dy[i] in registers and one store of dh[e, ..] per entry;
-// one entry per edge column is what makes every dh[e, :] written exactly once.  No LDS, no atomics, no scratch.
+// signalling NaN and may pick either zero).  The 16-byte route needs the arg rows on a 16-byte boundary too.  pool_bwd_x_kernel: the
+// same groups over the transposed CSR, each entry loading the group's slice of arg[i] and dy[i].  pool_bwd_edges_kernel: the groups over
+// the rows with the slices of arg[i] and dy[i] in registers and one store of dh[e, ..] per entry; one entry per edge column is what
+// makes every dh[e, :] written exactly once.
 #include "common.h"
+#include "row_groups.h"
 
 namespace {
-
-// the smallest power of two from 4 with 4 G >= F, at most a wave
-int pool_group_width(int32_t F)
-{
-    int G = 4;
-    while (G < 64 && 4 * G < F) G *= 2;
-    return G;
-}
 
 // y[r, :], arg[r, :] = the first maximum over row r of (rowptr, col) and its column; the value's row is col[k] (vertex form) or eid[k]
 template <int G, bool VEC, bool EDGE>
@@ -41,40 +29,28 @@ __global__ __launch_bounds__(256) void pool_fwd_kernel(int32_t n, const int32_t 
                                                        const int32_t *__restrict__ eid, const float *__restrict__ x, float *__restrict__ y,
                                                        int32_t *__restrict__ arg, int32_t F)
 {
-    constexpr int kRows = 256 / G;
-    const int lane = threadIdx.x & 63;
-    const int sub = lane & (G - 1), first = lane & ~(G - 1);
-    const int64_t row = (int64_t)blockIdx.x * kRows + threadIdx.x / G;
-    int32_t beg = 0, len = 0;
-    if (row < n) {
-        beg = rowptr[row];
-        len = rowptr[row + 1] - beg;
-    }
-    int32_t rounds = len;
-#pragma unroll
-    for (int o = 32; o >= G; o >>= 1) rounds = max(rounds, __shfl_xor(rounds, o));
-    rounds = __builtin_amdgcn_readfirstlane(rounds);               // the same in every lane: a scalar loop bound
+    const amp::RowGroup<G> rg(n, rowptr);
     for (int32_t f0 = 0; f0 < F; f0 += 4 * G) {
-        // this lane's columns, and where it reads them: a column past F reads the last valid place and is never stored
+        // written out: through LaneColumns the encoder's forward at F = 128 ran 0.6 - 1.0 % slower (profiles/row_groups_ab.txt)
         int32_t colv[4];
 #pragma unroll
-        for (int a = 0; a < 4; ++a) colv[a] = VEC ? f0 + 4 * sub + a : f0 + sub + G * a;
+        for (int a = 0; a < 4; ++a) colv[a] = VEC ? f0 + 4 * rg.sub + a : f0 + rg.sub + G * a;
         const int32_t at4 = min(colv[0], F - 4);                    // VEC only: F >= 4 there
         float best[4] = {0.f, 0.f, 0.f, 0.f};
         int32_t barg[4] = {-1, -1, -1, -1};
-        for (int32_t k0 = 0; k0 < rounds; k0 += G) {
+        for (int32_t k0 = 0; k0 < rg.rounds; k0 += G) {
             int32_t c = 0, s = 0;
-            if (k0 + sub < len) {
-                const int64_t k = (int64_t)beg + k0 + sub;
+            if (k0 + rg.sub < rg.len) {
+                const int64_t k = (int64_t)rg.beg + k0 + rg.sub;
                 c = col[k];
                 s = EDGE ? eid[k] : c;
             }
-            const int nj = min(G, rounds - k0);
+            const int nj = min(G, rg.rounds - k0);
             for (int j0 = 0; j0 < nj; j0 += 4)                      // four entries a step (G is a multiple of 4): their loads fly together
 #pragma unroll
             for (int j = j0; j < j0 + 4; ++j) {                     // entry order: k0, k0 + 1, ...
-                const int32_t cj = __shfl(c, first + j);
-                const int32_t sj = EDGE ? __shfl(s, first + j) : cj;
+                const int32_t cj = __shfl(c, rg.first + j);
+                const int32_t sj = EDGE ? __shfl(s, rg.first + j) : cj;
                 const float *src = x + (int64_t)sj * F;
                 float v[4];
                 if (VEC) {
@@ -84,7 +60,7 @@ __global__ __launch_bounds__(256) void pool_fwd_kernel(int32_t n, const int32_t 
 #pragma unroll
                     for (int a = 0; a < 4; ++a) v[a] = src[min(colv[a], F - 1)];
                 }
-                const bool use = k0 + j < len, none = k0 + j == 0;
+                const bool use = k0 + j < rg.len, none = k0 + j == 0;
 #pragma unroll
                 for (int a = 0; a < 4; ++a) {
                     const bool take = use && (none || v[a] > best[a] || (v[a] != v[a] && best[a] == best[a]));
@@ -93,9 +69,9 @@ __global__ __launch_bounds__(256) void pool_fwd_kernel(int32_t n, const int32_t 
                 }
             }
         }
-        if (row < n) {
-            float *dst = y + row * F;
-            int32_t *adst = arg ? arg + row * F : nullptr;
+        if (rg.row < n) {
+            float *dst = y + rg.row * F;
+            int32_t *adst = arg ? arg + rg.row * F : nullptr;
             if (VEC) {
                 if (colv[0] < F) {
                     *reinterpret_cast<float4 *>(dst + colv[0]) = make_float4(best[0], best[1], best[2], best[3]);
@@ -119,34 +95,23 @@ __global__ __launch_bounds__(256) void pool_bwd_x_kernel(int32_t n, const int32_
                                                          const int32_t *__restrict__ arg, const float *__restrict__ dy,
                                                          float *__restrict__ dx, int32_t F)
 {
-    constexpr int kRows = 256 / G;
-    const int lane = threadIdx.x & 63;
-    const int sub = lane & (G - 1), first = lane & ~(G - 1);
-    const int64_t row = (int64_t)blockIdx.x * kRows + threadIdx.x / G;
-    int32_t beg = 0, len = 0;
-    if (row < n) {
-        beg = t_rowptr[row];
-        len = t_rowptr[row + 1] - beg;
-    }
-    const int32_t me = (int32_t)row;                                // the column this group sums for: what arg must name
-    int32_t rounds = len;
-#pragma unroll
-    for (int o = 32; o >= G; o >>= 1) rounds = max(rounds, __shfl_xor(rounds, o));
-    rounds = __builtin_amdgcn_readfirstlane(rounds);
+    const amp::RowGroup<G> rg(n, t_rowptr);
+    const int32_t me = (int32_t)rg.row;                             // the column this group sums for: what arg must name
     for (int32_t f0 = 0; f0 < F; f0 += 4 * G) {
+        // written out: through LaneColumns this kernel's register allocation moves (profiles/row_groups_isa.txt)
         int32_t colv[4];
 #pragma unroll
-        for (int a = 0; a < 4; ++a) colv[a] = VEC ? f0 + 4 * sub + a : f0 + sub + G * a;
-        const int32_t at4 = min(colv[0], F - 4);
+        for (int a = 0; a < 4; ++a) colv[a] = VEC ? f0 + 4 * rg.sub + a : f0 + rg.sub + G * a;
+        const int32_t at4 = min(colv[0], F - 4);                    // VEC only: F >= 4 there
         float acc[4] = {0.f, 0.f, 0.f, 0.f};
-        for (int32_t k0 = 0; k0 < rounds; k0 += G) {
+        for (int32_t k0 = 0; k0 < rg.rounds; k0 += G) {
             int32_t i = 0;
-            if (k0 + sub < len) i = t_src[(int64_t)beg + k0 + sub];
-            const int nj = min(G, rounds - k0);
+            if (k0 + rg.sub < rg.len) i = t_src[(int64_t)rg.beg + k0 + rg.sub];
+            const int nj = min(G, rg.rounds - k0);
             for (int j0 = 0; j0 < nj; j0 += 4)
 #pragma unroll
             for (int j = j0; j < j0 + 4; ++j) {
-                const int64_t at = (int64_t)__shfl(i, first + j) * F;
+                const int64_t at = (int64_t)__shfl(i, rg.first + j) * F;
                 int32_t w[4];
                 float d[4];
                 if (VEC) {
@@ -162,7 +127,7 @@ __global__ __launch_bounds__(256) void pool_bwd_x_kernel(int32_t n, const int32_
                         d[a] = dy[at + f];
                     }
                 }
-                const bool use = k0 + j < len;
+                const bool use = k0 + j < rg.len;
 #pragma unroll
                 for (int a = 0; a < 4; ++a) {
                     const float sum = acc[a] + d[a];
@@ -170,8 +135,8 @@ __global__ __launch_bounds__(256) void pool_bwd_x_kernel(int32_t n, const int32_
                 }
             }
         }
-        if (row < n) {
-            float *dst = dx + row * F;
+        if (rg.row < n) {
+            float *dst = dx + rg.row * F;
             if (VEC) {
                 if (colv[0] < F) *reinterpret_cast<float4 *>(dst + colv[0]) = make_float4(acc[0], acc[1], acc[2], acc[3]);
             } else {
@@ -189,98 +154,44 @@ __global__ __launch_bounds__(256) void pool_bwd_edges_kernel(int32_t n, const in
                                                              const int32_t *__restrict__ eid, const int32_t *__restrict__ arg,
                                                              const float *__restrict__ dy, float *__restrict__ dh, int32_t F)
 {
-    constexpr int kRows = 256 / G;
-    const int lane = threadIdx.x & 63;
-    const int sub = lane & (G - 1), first = lane & ~(G - 1);
-    const int64_t row = (int64_t)blockIdx.x * kRows + threadIdx.x / G;
-    int32_t beg = 0, len = 0;
-    if (row < n) {
-        beg = rowptr[row];
-        len = rowptr[row + 1] - beg;
-    }
-    int32_t rounds = len;
-#pragma unroll
-    for (int o = 32; o >= G; o >>= 1) rounds = max(rounds, __shfl_xor(rounds, o));
-    rounds = __builtin_amdgcn_readfirstlane(rounds);
+    const amp::RowGroup<G> rg(n, rowptr);
     for (int32_t f0 = 0; f0 < F; f0 += 4 * G) {
-        int32_t colv[4];
-#pragma unroll
-        for (int a = 0; a < 4; ++a) colv[a] = VEC ? f0 + 4 * sub + a : f0 + sub + G * a;
-        const int32_t at4 = min(colv[0], F - 4);
+        const amp::LaneColumns<G, VEC> cols(rg.sub, f0, F);
         int32_t w[4] = {-1, -1, -1, -1};
         float d[4] = {0.f, 0.f, 0.f, 0.f};
-        if (len > 0) {                                              // an empty row has no entry to write for
-            const int32_t *wr = arg + row * F;
-            const float *dr = dy + row * F;
-            if (VEC) {
-                const int4 qa = *reinterpret_cast<const int4 *>(wr + at4);
-                const float4 qd = *reinterpret_cast<const float4 *>(dr + at4);
-                w[0] = qa.x, w[1] = qa.y, w[2] = qa.z, w[3] = qa.w;
-                d[0] = qd.x, d[1] = qd.y, d[2] = qd.z, d[3] = qd.w;
-            } else {
-#pragma unroll
-                for (int a = 0; a < 4; ++a) {
-                    const int32_t f = min(colv[a], F - 1);
-                    w[a] = wr[f];
-                    d[a] = dr[f];
-                }
-            }
-        }
-        for (int32_t k0 = 0; k0 < rounds; k0 += G) {
+        if (rg.len > 0) cols.load4(arg + rg.row * F, w, dy + rg.row * F, d);   // an empty row has no entry to write for
+        for (int32_t k0 = 0; k0 < rg.rounds; k0 += G) {
             int32_t c = 0, e = 0;
-            if (k0 + sub < len) {
-                const int64_t k = (int64_t)beg + k0 + sub;
+            if (k0 + rg.sub < rg.len) {
+                const int64_t k = (int64_t)rg.beg + k0 + rg.sub;
                 c = col[k];
                 e = eid[k];
             }
-            const int nj = min(G, rounds - k0);
+            const int nj = min(G, rg.rounds - k0);
             for (int j = 0; j < nj; ++j) {                          // entry order, though each dh row has one writer
-                const int32_t cj = __shfl(c, first + j);
-                const int32_t ej = __shfl(e, first + j);
-                if (k0 + j < len) {
-                    float *dst = dh + (int64_t)ej * F;
+                const int32_t cj = __shfl(c, rg.first + j);
+                const int32_t ej = __shfl(e, rg.first + j);
+                if (k0 + j < rg.len) {
                     float out[4];
 #pragma unroll
                     for (int a = 0; a < 4; ++a) out[a] = w[a] == cj ? d[a] : 0.f;
-                    if (VEC) {
-                        if (colv[0] < F) *reinterpret_cast<float4 *>(dst + colv[0]) = make_float4(out[0], out[1], out[2], out[3]);
-                    } else {
-#pragma unroll
-                        for (int a = 0; a < 4; ++a)
-                            if (colv[a] < F) dst[colv[a]] = out[a];
-                    }
+                    cols.store4(dh + (int64_t)ej * F, out);
                 }
             }
         }
     }
 }
 
-// one launch per (group width, load route): LAUNCH(W, V) names the kernel instance
-#define ATHENA_POOL_DISPATCH(LAUNCH)                  \
-    do {                                              \
-        switch (G) {                                  \
-        case 4: if (vec) LAUNCH(4, true); else LAUNCH(4, false); break;    \
-        case 8: if (vec) LAUNCH(8, true); else LAUNCH(8, false); break;    \
-        case 16: if (vec) LAUNCH(16, true); else LAUNCH(16, false); break; \
-        case 32: if (vec) LAUNCH(32, true); else LAUNCH(32, false); break; \
-        default: if (vec) LAUNCH(64, true); else LAUNCH(64, false); break; \
-        }                                             \
-    } while (0)
-
 // the forward of both forms: src names the rows of `values` (col for x, eid for h)
 template <bool EDGE>
 int pool_forward(const athena_mp_graph *g, int32_t F, const float *values, float *y, int32_t *arg)
 {
     if (g->n_rows == 0) return 0;
-    const int G = pool_group_width(F);
-    const dim3 grid((unsigned)(((int64_t)g->n_rows + 256 / G - 1) / (256 / G))), block(256);
-    hipStream_t st = amp::stream();
-    const bool vec = F % 4 == 0 && amp::aligned16(values, y) && amp::aligned16(arg);
-#define ATHENA_POOL_FWD(W, V)                                                                                                            \
-    hipLaunchKernelGGL((pool_fwd_kernel<W, V, EDGE>), grid, block, 0, st, g->n_rows, (const int32_t *)g->rowptr, (const int32_t *)g->col, \
-                       (const int32_t *)g->eid, values, y, arg, F)
-    ATHENA_POOL_DISPATCH(ATHENA_POOL_FWD);
-#undef ATHENA_POOL_FWD
+    const int G = amp::group_width(F);
+    amp::dispatch_group(G, F % 4 == 0 && amp::aligned16(values, y) && amp::aligned16(arg), [&](auto gw, auto v) {
+        hipLaunchKernelGGL((pool_fwd_kernel<gw(), v(), EDGE>), amp::group_grid(g->n_rows, G), dim3(256), 0, amp::stream(), g->n_rows,
+                           (const int32_t *)g->rowptr, (const int32_t *)g->col, (const int32_t *)g->eid, values, y, arg, F);
+    });
     AMP_LAUNCH_CHECK();
     return 0;
 }
@@ -289,11 +200,14 @@ int pool_forward(const athena_mp_graph *g, int32_t F, const float *values, float
 
 namespace amp {
 
-// what every entry checks first; the edge forms add the interpolation entries' conditions on the handle
+// what every entry checks first; the edge forms need one entry per edge column
 int pool_check(const char *who, const athena_mp_graph *g, int32_t F, bool edge_form)
 {
-    if (edge_form) return interp_check(who, g, nullptr, &F, nullptr);
-    AMP_REQUIRE(g != nullptr, "%s: null graph handle", who);
+    if (edge_form) {
+        if (int rc = edge_form_check(who, g)) return rc;
+    } else {
+        AMP_REQUIRE(g != nullptr, "%s: null graph handle", who);
+    }
     AMP_REQUIRE(F >= 1, "%s: F = %d: need at least one feature column", who, F);
     return 0;
 }
@@ -320,15 +234,11 @@ extern "C" int athena_mp_pool_max_bwd_x(const athena_mp_graph *g, int32_t F, con
     AMP_REQUIRE((g->nnz == 0 || (arg_dev != nullptr && dy_dev != nullptr)) && (g->n_cols == 0 || dx_dev != nullptr),
                 "pool_max_bwd_x: null array");
     if (g->n_cols == 0) return 0;
-    const int G = pool_group_width(F);
-    const dim3 grid((unsigned)(((int64_t)g->n_cols + 256 / G - 1) / (256 / G))), block(256);
-    hipStream_t st = amp::stream();
-    const bool vec = F % 4 == 0 && amp::aligned16(dy_dev, dx_dev) && amp::aligned16(arg_dev);
-#define ATHENA_POOL_BWD_X(W, V)                                                                                                     \
-    hipLaunchKernelGGL((pool_bwd_x_kernel<W, V>), grid, block, 0, st, g->n_cols, (const int32_t *)g->t_rowptr, (const int32_t *)g->t_src, \
-                       arg_dev, dy_dev, dx_dev, F)
-    ATHENA_POOL_DISPATCH(ATHENA_POOL_BWD_X);
-#undef ATHENA_POOL_BWD_X
+    const int G = amp::group_width(F);
+    amp::dispatch_group(G, F % 4 == 0 && amp::aligned16(dy_dev, dx_dev) && amp::aligned16(arg_dev), [&](auto gw, auto v) {
+        hipLaunchKernelGGL((pool_bwd_x_kernel<gw(), v()>), amp::group_grid(g->n_cols, G), dim3(256), 0, amp::stream(), g->n_cols,
+                           (const int32_t *)g->t_rowptr, (const int32_t *)g->t_src, arg_dev, dy_dev, dx_dev, F);
+    });
     AMP_LAUNCH_CHECK();
     return 0;
 }
@@ -338,15 +248,11 @@ extern "C" int athena_mp_pool_max_bwd_edges(const athena_mp_graph *g, int32_t F,
     if (int rc = amp::pool_check("pool_max_bwd_edges", g, F, true)) return rc;
     if (g->nnz == 0) return 0;                                      // no entry, so no edge column either: dh is empty
     AMP_REQUIRE(arg_dev != nullptr && dy_dev != nullptr && dh_dev != nullptr, "pool_max_bwd_edges: null array");
-    const int G = pool_group_width(F);
-    const dim3 grid((unsigned)(((int64_t)g->n_rows + 256 / G - 1) / (256 / G))), block(256);
-    hipStream_t st = amp::stream();
-    const bool vec = F % 4 == 0 && amp::aligned16(dy_dev, dh_dev) && amp::aligned16(arg_dev);
-#define ATHENA_POOL_BWD_EDGES(W, V)                                                                                                   \
-    hipLaunchKernelGGL((pool_bwd_edges_kernel<W, V>), grid, block, 0, st, g->n_rows, (const int32_t *)g->rowptr, (const int32_t *)g->col, \
-                       (const int32_t *)g->eid, arg_dev, dy_dev, dh_dev, F)
-    ATHENA_POOL_DISPATCH(ATHENA_POOL_BWD_EDGES);
-#undef ATHENA_POOL_BWD_EDGES
+    const int G = amp::group_width(F);
+    amp::dispatch_group(G, F % 4 == 0 && amp::aligned16(dy_dev, dh_dev) && amp::aligned16(arg_dev), [&](auto gw, auto v) {
+        hipLaunchKernelGGL((pool_bwd_edges_kernel<gw(), v()>), amp::group_grid(g->n_rows, G), dim3(256), 0, amp::stream(), g->n_rows,
+                           (const int32_t *)g->rowptr, (const int32_t *)g->col, (const int32_t *)g->eid, arg_dev, dy_dev, dh_dev, F);
+    });
     AMP_LAUNCH_CHECK();
     return 0;
 }
