@@ -8,10 +8,12 @@
 // Why: the unfused step is HBM bound as a whole; the dense kernels are matrix-pipe bound
 // and the aggregation is fabric bound, but run back to back they cannot overlap and P / dP make a
 // round trip through HBM.  Here a 16-wave workgroup per CU keeps W resident in LDS (K, N = 128: 67.6 KB)
-// and software-pipelines 64-row chunks through two LDS tile buffers:
-//   gather (every wave: one row pair, same half-wave-per-row mapping and CSR-order summation as
-//           csr_gather_agg: P is bit-identical to the unfused kernel) -> LDS tile [32][K+4] (+ P rows
-//           to HBM, forward)
+// and software-pipelines 32-row chunks (K = 64: 64-row chunks) through two LDS tile buffers:
+//   gather (every wave: one row pair, the same CSR-order summation as csr_gather_agg: P is bit-identical
+//           to the unfused kernel.  K = 128: the whole wave gathers one row at a time, 8 bytes per lane,
+//           with the row's start, length, entry ids and coefficients in scalar registers; K = 64: a
+//           quarter-wave per row, 16 bytes per lane, ids and coefficients by cross-lane shuffle)
+//           -> LDS tile [32][K+4] (+ P rows to HBM, forward)
 //   MFMA   (every wave: one 16x16 block of the chunk's 32x128 output, v_mfma_f32_16x16x4_f32 against
 //           the resident W) while the first 16 row loads of the NEXT chunk are already in flight.
 // One __syncthreads per chunk; row pointers and the first index block are prefetched a chunk ahead, so
@@ -19,6 +21,7 @@
 // with 3-pair gather waves, and 64-row chunks with two pairs per wave -- measured 1.40 / 1.03 ms
 // against 0.98 ms for this one and 1.12 ms unfused.)
 #include <algorithm>
+#include <type_traits>
 
 #include "common.h"
 
@@ -39,10 +42,25 @@ constexpr int kUn = 4;
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// 32-row chunks, one row pair per wave; the first kFirst row loads of the NEXT chunk are issued before
-// the matrix work of the CURRENT chunk and consumed after it.
+// 32-row chunks, one row pair per wave; the first kFirst row loads of each row of the NEXT chunk are issued
+// before the matrix work of the CURRENT chunk and consumed after it.
 #define KFIRST 16
 constexpr int kFirst = KFIRST;
+
+// f(0), f(1), ... f(min(n, K1) - 1) with the slot number a compile-time constant and n in a scalar register: slot k sits inside
+// the branch of slot k - 1, so a row leaves the chain at its own length by ONE scalar branch and no slot is predicated.
+// (Sixteen guarded slots side by side -- `if (k < n)` in an unrolled loop -- compile into a chain that carries its state in
+// mask registers and waits for all but one outstanding load before every slot; an unrolled loop with `break` is not unrolled
+// at all and its registers become a scratch array.)
+template <int K0, int K1, class F> __device__ __forceinline__ void first_slots(int n, F &&f)
+{
+    if constexpr (K0 < K1) {
+        if (K0 < n) {
+            f(std::integral_constant<int, K0>{});
+            first_slots<K0 + 1, K1>(n, f);
+        }
+    }
+}
 
 // Nontemporal streams, each decided by the A/B in profiles/r04_kipf_nt_ab.txt: noted where they are used.
 template <int N, bool COEF, int ACT, bool BUF>
@@ -68,7 +86,8 @@ __global__ __launch_bounds__(1024) void agg_gemm_kernel(const int32_t *__restric
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float *Bs = lds;                      // [N][LD]
     float *Ts = lds + N * LD;             // [2 buffers][CH rows][LD]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // in a scalar register: what follows from it is wave-uniform
     const int h = lane / G, gl = lane & (G - 1);
 
     {   // W resident in LDS as [n][K+4]
@@ -103,7 +122,8 @@ __global__ __launch_bounds__(1024) void agg_gemm_kernel(const int32_t *__restric
     const float bv = bias ? bias[16 * ct + l15] : 0.0f;
     const int lrow = RPW * wave + h;      // this lane group's row inside a chunk
 
-    // per-chunk gather state of this half-wave's row
+    // The lane-group gather, used at K = 64 (the K = 128 gather follows it): G lanes of float4 per row, RPW rows side by side in
+    // a wave.  Per-chunk gather state of this lane group's row
     int start = 0, len = 0, idx0 = -1;
     float c0 = 0.0f;
     auto load_state = [&](int64_t chunk) {
@@ -218,6 +238,110 @@ __global__ __launch_bounds__(1024) void agg_gemm_kernel(const int32_t *__restric
             __builtin_nontemporal_store(acc, reinterpret_cast<v4f *>(P + row * K + 4 * gl));
     };
 
+    // K = 128: a row is gathered by the WHOLE wave, 8 bytes per lane, the wave's two rows one after the other.  Everything about
+    // a row is then wave-uniform: start and length come from rowptr by scalar loads, an entry's id and coefficient reach a scalar
+    // register by v_readlane from the lane that loaded them (lane j holds entry j of the row's current 64-entry block: the same
+    // coalesced, nontemporal read as above), the id goes into the row load as its scalar offset, and a row ends at its own length
+    // by a scalar branch -- no cross-lane shuffle, no predicated or zero-filled slot, no per-load address arithmetic.  Per entry
+    // that is v_readlane + buffer_load (+ two scalar instructions) when issued and v_readlane + v_pk_mul_f32 + v_pk_add_f32 when
+    // summed.  Per chunk and wave the lane-group form above executed 527 instructions whatever the row lengths (all 16 slots of
+    // a row pair: 273 vector, 33 ds_bpermute), this one executes about 255 and 12 per entry: at configs[1]'s 20 entries per wave
+    // about 495, of them 144 vector (v_readlane among them) and no ds_bpermute.  configs[1]: step 2.070 -> 1.996 ms, forward
+    // 0.920 -> 0.897 ms, reverse 0.839 -> 0.801 ms (profiles/row_per_wave_ab.txt).
+    // Measured and dropped: the first kFirst ids and coefficients of both rows read by scalar loads a chunk ahead (s_load_dword
+    // under the same chain, no v_readlane): 64 scalar registers live across the matrix work do not fit beside the kernel's 60, the
+    // forward launch spills them through v_writelane / v_readlane and takes 1.007 ms (parent 0.920); the coefficient-free reverse
+    // launch fits (90 scalar registers) and takes 0.802 ms, the same as with v_readlane.
+    typedef float v2f __attribute__((ext_vector_type(2)));
+    int wstart[2] = {0, 0}, wlen[2] = {0, 0}, widx[2] = {0, 0};
+    float wcoef[2] = {0.0f, 0.0f};
+    v2f wv[2][kFirst];
+    auto lane_f = [](float f, int l) -> float { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(f), l)); };
+    auto w_load_entries = [&](int r, int off, int &my_idx, float &my_c) {   // entry off + lane of row r, if the row has it
+        my_idx = 0; my_c = 0.0f;
+        if (off + lane < wlen[r]) {
+            if constexpr (COEF) {
+                my_idx = __builtin_nontemporal_load(idx + wstart[r] + off + lane);
+                my_c = __builtin_nontemporal_load(coef + wstart[r] + off + lane);
+            } else {
+                my_idx = idx[wstart[r] + off + lane];
+            }
+        }
+    };
+    auto w_load_state = [&](int64_t chunk) {
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            wstart[r] = 0; wlen[r] = 0;
+            const int64_t row = chunk * CH + 2 * wave + r;
+            if (chunk < n_chunks && row < n_rows) {
+                wstart[r] = __builtin_amdgcn_readfirstlane(rowptr[row]);
+                wlen[r] = __builtin_amdgcn_readfirstlane(rowptr[row + 1]) - wstart[r];
+            }
+            w_load_entries(r, 0, widx[r], wcoef[r]);
+        }
+    };
+    auto w_load_row = [&](int u) -> v2f {     // u in a scalar register
+        if constexpr (BUF) {
+            typedef int v2i_ __attribute__((ext_vector_type(2)));
+            const v2i_ t = __builtin_amdgcn_raw_buffer_load_b64(xrsrc, 8 * lane, (int)((uint32_t)u << 9), 0);   // offsets past x_bytes read as zero
+            return __builtin_bit_cast(v2f, t);
+        } else {
+            return *reinterpret_cast<const v2f *>(x + (int64_t)u * K + 2 * lane);
+        }
+    };
+    auto w_issue_first = [&]() {          // row loads of entries 0 .. kFirst-1 of both rows (no waits)
+        // (both rows' first ids are read before any row load is issued: the wait for the entry loads of load_state stands here,
+        // once, and not between the two rows' loads)
+        const int u0[2] = {__builtin_amdgcn_readlane(widx[0], 0), __builtin_amdgcn_readlane(widx[1], 0)};
+#pragma unroll
+        for (int r = 0; r < 2; ++r)
+            first_slots<0, kFirst>(wlen[r], [&](auto k) { wv[r][k] = w_load_row(k == 0 ? u0[r] : __builtin_amdgcn_readlane(widx[r], k)); });
+    };
+    auto w_finish_store = [&](int64_t chunk, int buf) {   // CSR-order accumulation of both rows, tile and P rows out
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            const int len = wlen[r];
+            v2f acc = {0.0f, 0.0f};
+            first_slots<0, kFirst>(len, [&](auto k) {
+                if constexpr (COEF) acc = acc + lane_f(wcoef[r], k) * wv[r][k];
+                else acc = acc + wv[r][k];
+            });
+            // entries kFirst.. of long rows, kUn row loads in flight: entries j .. cnt-1 (j < cnt) of one 64-entry block
+            auto stream = [&](int my_idx, float my_c, int j, int cnt) {
+                do {
+                    const int n = min(kUn, cnt - j);
+                    v2f w[kUn];
+                    first_slots<0, kUn>(n, [&](auto k) { w[k] = w_load_row(__builtin_amdgcn_readlane(my_idx, j + k)); });
+                    first_slots<0, kUn>(n, [&](auto k) {
+                        if constexpr (COEF) acc = acc + lane_f(my_c, j + k) * w[k];
+                        else acc = acc + w[k];
+                    });
+                } while ((j += kUn) < cnt);
+            };
+            if (len > kFirst) {
+                stream(widx[r], wcoef[r], kFirst, min(64, len));
+                for (int off = 64; off < len; off += 64) {
+                    int my_idx;
+                    float my_c;
+                    w_load_entries(r, off, my_idx, my_c);
+                    stream(my_idx, my_c, 0, min(64, len - off));
+                }
+            }
+            const int wrow = 2 * wave + r;
+            const int64_t row = chunk * CH + wrow;
+            *reinterpret_cast<v2f *>(Ts + (buf * CH + wrow) * LD + 2 * lane) = acc;
+            if (P != nullptr && chunk < n_chunks && row < n_rows)   // one contiguous 512 B row per store, nontemporal as above
+                __builtin_nontemporal_store(acc, reinterpret_cast<v2f *>(P + row * K + 2 * lane));
+        }
+    };
+    constexpr bool kWaveRow = K == 128;
+    auto state_of = [&](int64_t chunk) { if constexpr (kWaveRow) w_load_state(chunk); else load_state(chunk); };
+    auto issue = [&]() { if constexpr (kWaveRow) w_issue_first(); else issue_first(); };
+    auto gather_into = [&](int64_t chunk, int buf) {
+        if constexpr (kWaveRow) w_finish_store(chunk, buf);
+        else store_row(chunk, buf, finish());
+    };
+
     // (Measured and dropped: walking the rows longest first so that the rows of a chunk have equal lengths -- 6 % slower,
     // every level of the walk turns into a random access; walking only the 2 % of rows longer than the prefetched block
     // last, in chunks of their own -- no change: the exposed round of loads such a row costs its workgroup is not what a
@@ -233,16 +357,21 @@ __global__ __launch_bounds__(1024) void agg_gemm_kernel(const int32_t *__restric
     auto draw = [&]() -> int64_t { return (int64_t)atomicAdd(ticket, 1ull); };
     if (tid == 0) { s_ticket[0] = draw(); s_ticket[1] = draw(); s_ticket[2] = draw(); }
     __syncthreads();
-    int64_t k0 = s_ticket[0], k1 = s_ticket[1], k2 = s_ticket[2];
-    load_state(k0);
-    issue_first();
-    store_row(k0, 0, finish());
-    load_state(k1);
+    auto ticket_at = [&](int i) -> int64_t {              // the same in every lane: kept in scalar registers
+        const uint64_t t = (uint64_t)s_ticket[i];
+        return (int64_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(t >> 32)) << 32) |
+                         (uint32_t)__builtin_amdgcn_readfirstlane((int)t));
+    };
+    int64_t k0 = ticket_at(0), k1 = ticket_at(1), k2 = ticket_at(2);
+    state_of(k0);
+    issue();
+    gather_into(k0, 0);
+    state_of(k1);
     __syncthreads();
     for (int it = 0; k0 < n_chunks; ++it) {
         const int64_t chunk = k0;
         const int buf = it & 1;
-        issue_first();                                      // rows of k1
+        issue();                                            // rows of k1
         auto matrix_work = [&]() {
             const float *arow = Ts + (buf * CH + 16 * rb + l15) * LD + KG * g4;
             const float *brow = Bs + (16 * ct + l15) * LD + KG * g4;
@@ -265,13 +394,13 @@ __global__ __launch_bounds__(1024) void agg_gemm_kernel(const int32_t *__restric
         // (Measured and dropped: waves 4-7 and 12-15 gathering chunk k1 before the matrix work of k0, so that every SIMD holds
         // two waves on each job -- configs[1] 0.936 / 0.884 ms with, 0.930 / 0.890 ms without (forward / reverse).)
         matrix_work();
-        store_row(k1, buf ^ 1, finish());
-        load_state(k2);
+        gather_into(k1, buf ^ 1);
+        state_of(k2);
         if (tid == 0) s_ticket[it & 1] = draw();
         __syncthreads();
         k0 = k1;
         k1 = k2;
-        k2 = s_ticket[it & 1];
+        k2 = ticket_at(it & 1);
     }
 }
 
