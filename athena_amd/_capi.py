@@ -57,6 +57,11 @@ _PROTOS = {
     "athena_mp_farthest_points": [_i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
     "athena_mp_farthest_points_host": [_i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
     "athena_mp_fps_stats": [_vp],
+    "athena_mp_grid_clusters": [_i32, _i32, _vp, _i32, _vp, _f32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "athena_mp_grid_clusters_grad": [_i32, _i32, _i32, _vp, _vp, _vp, _vp],
+    "athena_mp_grid_clusters_host": [_i32, _i32, _vp, _i32, _vp, _f32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "athena_mp_grid_clusters_grad_host": [_i32, _i32, _i32, _vp, _vp, _vp, _vp],
+    "athena_mp_grid_clusters_stats": [_vp],
     "athena_mp_periodic_pairs": [_i32, _i32, _vp, _vp, _vp, _vp, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp],
     "athena_mp_periodic_graph_host": [_i32, _i32, _vp, _vp, _vp, _vp, _f32, _f32, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp,
                                       _vp],

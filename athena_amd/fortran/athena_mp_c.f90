@@ -57,6 +57,8 @@ module athena_mp_c
   public :: athena_mp_knn_pairs_batched, athena_mp_knn_pairs, athena_mp_knn_graph_batched_host, athena_mp_knn_stats
   public :: athena_mp_knn_pairs_bipartite, athena_mp_knn_graph_bipartite_host
   public :: athena_mp_farthest_points, athena_mp_farthest_points_host, athena_mp_fps_stats
+  public :: athena_mp_grid_clusters, athena_mp_grid_clusters_grad, athena_mp_grid_clusters_host, athena_mp_grid_clusters_grad_host
+  public :: athena_mp_grid_clusters_stats
   public :: athena_mp_interp_weights, athena_mp_interp_fwd, athena_mp_interp_bwd_x, athena_mp_interp_bwd_coords
   public :: athena_mp_interp_host, athena_mp_interp_bwd_host
   public :: athena_mp_pool_max_fwd, athena_mp_pool_max_edges_fwd, athena_mp_pool_max_bwd_x, athena_mp_pool_max_bwd_edges
@@ -690,6 +692,62 @@ module athena_mp_c
      end function
      !! the last farthest-point call: samples, chunk tests of the stream route, tests that skipped, clouds on the stream route
      integer(c_int) function athena_mp_fps_stats(out) bind(C, name="athena_mp_fps_stats")
+       import :: c_int, c_int64_t
+       integer(c_int64_t), intent(out) :: out(4)
+     end function
+     !! voxel-grid clusters of a batch of clouds (definition: include/athena_mp.h): every non-empty cubic cell of edge size of a
+     !! cloud is one cluster, numbered by (cloud, cell) with the first axis fastest, members in index order.  offsets
+     !! (n_clouds + 1) and origin (c_loc of dim real32, or c_null_ptr: each cloud's own lower corner) on the host; points (dim, n)
+     !! on the device; cluster (n), pairs (2, n) = (cluster, point), rowptr (capacity + 1, 0-based), weights (n), centroid
+     !! (dim, capacity), nearest (capacity) and cell (dim, capacity) on the device, each may be c_null_ptr (all seven: the counts
+     !! only); cluster_offsets (c_loc of n_clouds + 1 int32) and origin_out (c_loc of (dim, n_clouds) real32) on the host, or
+     !! c_null_ptr
+     integer(c_int) function athena_mp_grid_clusters(n_clouds, n, offsets, dim, points_dev, size, origin, capacity, cluster_dev, &
+          pairs_dev, rowptr_dev, weights_dev, centroid_dev, nearest_dev, cell_dev, cluster_offsets, origin_out, n_clusters) &
+          bind(C, name="athena_mp_grid_clusters")
+       import :: c_int, c_int32_t, c_int64_t, c_float, c_ptr
+       integer(c_int32_t), value :: n_clouds, n, dim
+       integer(c_int32_t), intent(in) :: offsets(*)
+       real(c_float), value :: size
+       integer(c_int64_t), value :: capacity
+       type(c_ptr), value :: points_dev, origin, cluster_dev, pairs_dev, rowptr_dev, weights_dev, centroid_dev, nearest_dev, cell_dev
+       type(c_ptr), value :: cluster_offsets, origin_out
+       integer(c_int64_t), intent(out) :: n_clusters
+     end function
+     !! its reverse step: dpoints(:, j) = dcentroid(:, cluster(j)) / count of that cluster, count from the differences of rowptr
+     integer(c_int) function athena_mp_grid_clusters_grad(n, dim, n_clusters, cluster_dev, rowptr_dev, dcentroid_dev, dpoints_dev) &
+          bind(C, name="athena_mp_grid_clusters_grad")
+       import :: c_int, c_int32_t, c_ptr
+       integer(c_int32_t), value :: n, dim, n_clusters
+       type(c_ptr), value :: cluster_dev, rowptr_dev, dcentroid_dev, dpoints_dev
+     end function
+     !! the same with host arrays: points (dim, n) -> adj_ia (capacity + 1, 1-based), adj_ja (2, n) = (point, edge id), and
+     !! cluster (n), weights (n), centroid (dim, capacity), nearest (capacity), cell (dim, capacity), cluster_offsets
+     !! (n_clouds + 1), origin_out (dim, n_clouds) (c_null_ptr: not wanted); adj_ja = c_null_ptr queries n_clusters,
+     !! cluster_offsets and origin_out
+     integer(c_int) function athena_mp_grid_clusters_host(n_clouds, n, offsets, dim, points, size, origin, capacity, cluster, adj_ia, &
+          adj_ja, weights, centroid, nearest, cell, cluster_offsets, origin_out, n_clusters) &
+          bind(C, name="athena_mp_grid_clusters_host")
+       import :: c_int, c_int32_t, c_int64_t, c_float, c_ptr
+       integer(c_int32_t), value :: n_clouds, n, dim
+       integer(c_int32_t), intent(in) :: offsets(*)
+       real(c_float), intent(in) :: points(dim, *)
+       real(c_float), value :: size
+       integer(c_int64_t), value :: capacity
+       type(c_ptr), value :: origin, cluster, adj_ia, adj_ja, weights, centroid, nearest, cell, cluster_offsets, origin_out
+       integer(c_int64_t), intent(out) :: n_clusters
+     end function
+     !! ... and its reverse step: cluster (n), rowptr (n_clusters + 1: adj_ia serves), dcentroid (dim, n_clusters) -> dpoints (dim, n)
+     integer(c_int) function athena_mp_grid_clusters_grad_host(n, dim, n_clusters, cluster, rowptr, dcentroid, dpoints) &
+          bind(C, name="athena_mp_grid_clusters_grad_host")
+       import :: c_int, c_int32_t, c_float
+       integer(c_int32_t), value :: n, dim, n_clusters
+       integer(c_int32_t), intent(in) :: cluster(*), rowptr(*)
+       real(c_float), intent(in) :: dcentroid(dim, *)
+       real(c_float), intent(out) :: dpoints(dim, *)
+     end function
+     !! the last grid-cluster call: clusters, key bits sorted, radix passes, members of the largest cluster
+     integer(c_int) function athena_mp_grid_clusters_stats(out) bind(C, name="athena_mp_grid_clusters_stats")
        import :: c_int, c_int64_t
        integer(c_int64_t), intent(out) :: out(4)
      end function

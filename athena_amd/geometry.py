@@ -49,7 +49,19 @@ the maximum over each sample's neighbourhood, with the arg-max that the reverse 
     p = point_sets_grad(handle, g["coords"]);  p["queries"], p["sources"]
 
 pool_max(handle, x=...) takes per-vertex values instead (on any handle, square ones too) and pool_max_grad(..., to="x") is its
-reverse.  edge_features(..., x_queries=..., relative=True) makes EdgeConv's input (x_j - x_i, x_i)."""
+reverse.  edge_features(..., x_queries=..., relative=True) makes EdgeConv's input (x_j - x_i, x_i).
+
+For LARGE clouds the coarse set comes from a voxel grid instead (athena_amd/csrc/grid_clusters.hip): O(n), no dependent steps, one
+coarse point -- the centroid -- per non-empty cubic cell, and the membership as the pooling handle:
+
+    handle, centroid, cluster_offsets, cluster, weights = DeviceGraph.from_grid_clusters(points, size, offsets)
+    y, arg = pool_max(handle, x=x)                                      # [n_clusters, F]: max pooling; or the mean:
+    y = interpolate(handle, weights, x)                                 # weights[e] = 1 / the members of the pair's cluster
+    ... the coarse level works on (centroid, y)
+    up, coords, eoff = DeviceGraph.from_point_sets_knn(points, centroid, k=3, query_offsets=offsets, source_offsets=cluster_offsets)
+    w, wsum = interp_weights(up, coords);  z = interpolate(up, w, y_coarse)             # the way up, [n_points, F]
+    ... the reverse pass returns dcentroid [n_clusters, dim]
+    dpoints = grid_clusters_grad(cluster, handle, dcentroid)            # [n_points, dim]"""
 import ctypes as C
 
 import numpy as np
@@ -398,6 +410,34 @@ def farthest_points(points, offsets=None, n_samples=None, ratio=None, start=None
                ptr(sqdist), ptr(cover))
     out = (sample, sample_points, soff, cover)
     return out + (sqdist,) if want_sqdist else out
+
+
+def grid_clusters_grad(cluster, rowptr_or_handle, dcentroid, out=None):
+    """The reverse of the centroids of DeviceGraph.from_grid_clusters (athena_mp_grid_clusters_grad): dcentroid [m, dim] float32 on
+    the device -> dpoints [n, dim], dpoints[j] = dcentroid[c] / the members of c, c = cluster[j]; every bit is defined.  cluster [n]
+    int32 (1-based) as from_grid_clusters returned it; rowptr_or_handle: its handle, or a contiguous int32 device tensor [m + 1]
+    whose differences are the clusters' sizes.  out: a contiguous float32 device tensor [n, dim] to write into."""
+    import torch
+
+    if isinstance(rowptr_or_handle, torch.Tensor):
+        rowptr = rowptr_or_handle
+    else:
+        rowptr = getattr(rowptr_or_handle, "cluster_rowptr", None)
+        if rowptr is None:                       # any handle with these rows: its forward CSR's row pointer, through the host
+            rowptr = torch.from_numpy(np.ascontiguousarray(rowptr_or_handle.export("rowptr"), dtype=np.int32)).to(dcentroid.device)
+    m = int(rowptr.shape[0]) - 1
+    rowptr = _device_i32(rowptr, (m + 1,), "rowptr")
+    dcentroid = _device_f32(dcentroid, (m, None), "dcentroid")
+    dim = int(dcentroid.shape[1])
+    n = int(cluster.shape[0]) if isinstance(cluster, torch.Tensor) and cluster.dim() == 1 else -1
+    cluster = _device_i32(cluster, (max(n, 0),), "cluster")
+    if out is None:
+        out = torch.empty((n, dim), dtype=torch.float32, device=dcentroid.device)
+    out = _device_f32(out, (n, dim), "out")
+    _capi.use_torch_stream()
+    _capi.call("athena_mp_grid_clusters_grad", n, dim, m, C.c_void_p(cluster.data_ptr()), C.c_void_p(rowptr.data_ptr()),
+               C.c_void_p(dcentroid.data_ptr()), C.c_void_p(out.data_ptr()))
+    return out
 
 
 def cover_radius(cover_sqdist):

@@ -689,6 +689,73 @@ class DeviceGraph:
         return out
 
     @classmethod
+    def from_grid_clusters(cls, points, size, offsets=None, origin=None, want_nearest=False, want_cells=False, device=0):
+        """A batch of point clouds -> its voxel-grid clusters and the directed, rectangular device handle of their membership,
+        without the list leaving HBM (athena_mp_grid_clusters, then athena_mp_graph_create_bipartite_dev): every non-empty cubic
+        cell of edge `size` of a cloud is one row, its points the row's columns in index order; the definition is in
+        include/athena_mp.h.  points [n, dim] float32, dim 1..3: a numpy array, or a torch tensor already on the device; offsets
+        [B + 1] 0-based on the host (None: one cloud), empty clouds allowed; origin [dim]: the grid's corner for every cloud
+        (None: each cloud's own lower corner).  One call into buffers of n clusters, narrowed afterwards.  Returns (handle,
+        centroid, cluster_offsets, cluster, weights) and, when asked for, nearest and cells last: handle.n_rows = m clusters,
+        n_cols = n, edge e = pair e; centroid [m, dim] float32, cluster [n] int32 (1-based) and weights [n] float32 (1 / the
+        members of the pair's cluster) on the device; cluster_offsets numpy int32 [B + 1], what the query_offsets= /
+        source_offsets= arguments of from_point_sets / from_point_sets_knn take for the centroids; nearest [m] int32, the member
+        nearest each centroid as a 1-based global point id; cells [m, dim] int32.  pool_max(handle, x=x) is max pooling over the
+        clusters, interpolate(handle, weights, x) mean pooling.  The handle keeps rowptr [m + 1] int32 on the device as
+        handle.cluster_rowptr: geometry.grid_clusters_grad takes the handle."""
+        import torch
+
+        _capi.init(device)
+        dev = torch.device("cuda", device)
+        if isinstance(points, torch.Tensor):
+            pts = points.to(dev, torch.float32).contiguous()
+        else:
+            pts = torch.from_numpy(np.ascontiguousarray(points, dtype=np.float32)).to(dev)
+        if pts.dim() != 2:
+            raise ValueError("points must be [n, dim]")
+        n, dim = int(pts.shape[0]), int(pts.shape[1])
+        off = np.array([0, n], np.int32) if offsets is None else np.ascontiguousarray(offsets, dtype=np.int32)
+        if off.ndim != 1 or off.size < 1:
+            raise ValueError("offsets must be [B + 1]")
+        B = int(off.size - 1)
+        org = None
+        if origin is not None:
+            org = np.ascontiguousarray(origin, dtype=np.float32)
+            if org.shape != (dim,):
+                raise ValueError("origin must hold one coordinate per axis")
+        _capi.use_torch_stream()
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        vp = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+        cluster = torch.empty((n,), dtype=torch.int32, device=dev)
+        pairs = torch.empty((n, 2), dtype=torch.int32, device=dev)             # the memory of a column-major [2, n]
+        rowptr = torch.empty((n + 1,), dtype=torch.int32, device=dev)
+        weights = torch.empty((n,), dtype=torch.float32, device=dev)
+        centroid = torch.empty((n, max(dim, 1)), dtype=torch.float32, device=dev)
+        nearest = torch.empty((n,), dtype=torch.int32, device=dev) if want_nearest else None
+        cells = torch.empty((n, max(dim, 1)), dtype=torch.int32, device=dev) if want_cells else None
+        coff = np.empty(B + 1, np.int32)
+        m = C.c_int64()
+        _capi.call("athena_mp_grid_clusters", B, n, vp(off), dim, ptr(pts), float(size), vp(org), n, ptr(cluster), ptr(pairs), ptr(rowptr),
+                   ptr(weights), ptr(centroid), ptr(nearest), ptr(cells), vp(coff), None, C.byref(m))
+        m = int(m.value)
+        centroid = centroid[:m, :dim].clone()                                  # narrowed: the buffers of n clusters go back
+        self = cls.__new__(cls)
+        ia = np.empty(m + 1, np.int32)
+        h = C.c_void_p()
+        _capi.call("athena_mp_graph_create_bipartite_dev", m, n, n, ptr(pairs), vp(ia), None, 0, C.byref(h))
+        self.handle = h
+        self.n_rows, self.n_cols = m, n
+        self.nnz = n
+        self.n_edge_cols = n
+        self.cluster_rowptr = rowptr[:m + 1].clone()
+        out = (self, centroid, coff, cluster, weights)
+        if want_nearest:
+            out += (nearest[:m].clone(),)
+        if want_cells:
+            out += (cells[:m, :dim].clone(),)
+        return out
+
+    @classmethod
     def from_point_clouds_knn(cls, points, offsets, k, radius=None, mode="union", add_self_loops=False, want_adjacency=False,
                               want_neighbours=False, device=0):
         """A batch of point clouds -> one block-diagonal k-nearest-neighbour device handle without the pair list leaving HBM

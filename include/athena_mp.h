@@ -327,6 +327,71 @@ int athena_mp_farthest_points_host(int32_t n_clouds, int32_t n, const int32_t *o
  * a cloud too large for the register route; one test per chunk and step), out[2] = the tests that skipped their chunk, out[3] =
  * clouds that took the stream route. */
 int athena_mp_fps_stats(int64_t out[4]);
+/* Voxel-grid clusters of a batch of point clouds on the device (grid_clusters.hip): every cloud is cut into cubic cells of edge
+ * `size`, every non-empty cell is one coarse point -- the centroid of its members -- and the membership is the pooling graph: grid
+ * subsampling / voxel pooling, the O(n) coarsening of large clouds beside athena_mp_farthest_points, with no dependent steps.  The
+ * membership list is what athena_mp_graph_create_bipartite_dev takes; on that handle athena_mp_pool_max_fwd is max pooling and
+ * athena_mp_interp_fwd with `weights` is mean pooling.  Every implementation gives the same arrays.
+ *   Inputs: points [n, dim] fp32 row-major on the device, dim in 1..3; offsets [n_clouds + 1] int32 on the HOST, 0-based, as in
+ *   athena_mp_radius_pairs_batched (empty clouds allowed anywhere); size fp32 > 0, one for all clouds; origin_host [dim] fp32 on the
+ *   HOST, or NULL.
+ *   The cell of a point, every operation rounded to fp32 on its own: inv = 1 / size.  Per non-empty cloud b and axis k, lo_k = the
+ *   smallest k-th coordinate of the cloud's points with +0 added (-0 becomes +0) and hi_k the largest; with an origin, lo_k =
+ *   origin_k for every cloud.  The cell of point j is c_k = floor((p_jk - lo_k) * inv).  The cloud has nc_k = floor((hi_k - lo_k) *
+ *   inv) + 1 cells along axis k -- rounding is monotone, so the largest c_k that occurs is exactly nc_k - 1 -- and N_b = nc_0 nc_1
+ *   nc_2 cells in all.
+ *   Clusters: a cluster is a non-empty cell of a cloud.  Clusters are numbered, 1-based and over the whole batch, in ascending
+ *   order of (cloud, c_{dim-1}, ..., c_0): c_0 varies fastest.  Inside a cluster the members are in ascending point index.  m is
+ *   the number of clusters, count_c the members of cluster c.
+ *   Outputs, on the device unless marked, each may be NULL alone:
+ *     cluster [n] int32              the cluster of each point
+ *     pairs [2, n] int32             column-major, 1-based: (cluster, point) in lexicographic order -- the list
+ *                                    athena_mp_graph_create_bipartite_dev(n_rows = m, n_cols = n, n_pairs = n, ...) takes
+ *     rowptr [capacity + 1] int32    0-based: rowptr[c] = the pairs in front of cluster c, rowptr[m] = n; m + 1 entries are written
+ *     weights [n] fp32               one per pair: 1 / fl(count) of the pair's cluster (mean pooling through athena_mp_interp_fwd)
+ *     centroid [capacity, dim] fp32  lo_k + S_k / fl(count), S_k the SEQUENTIAL sum, from +0, of (p_jk - lo_k) over the members in
+ *                                    index order.  Relative to lo on purpose: the plain sum of coordinates around 1e6 loses them
+ *     nearest [capacity] int32       the member with the smallest s(p_j, centroid), s the squared distance of
+ *                                    athena_mp_radius_pairs (d = p_j - centroid, s = ((d0*d0) + d1*d1) + d2*d2), ties to the smaller
+ *                                    index: a 1-based global point id, as `sample` of athena_mp_farthest_points
+ *     cell [capacity, dim] int32     the cluster's c_k
+ *     cluster_offsets [n_clouds + 1] int32 on the HOST: the clusters in front of each cloud; cluster_offsets[n_clouds] = m
+ *     origin_out [n_clouds, dim] fp32 on the HOST: the lo used (0 for an empty cloud)
+ *     *n_clusters_out = m (never NULL)
+ *   Of the arrays with capacity rows, m are written.  All seven device outputs NULL: a size query (m, cluster_offsets, origin_out).
+ * Refused with a message: dim outside 1..3; a size that is not finite or <= 0, or whose inverse is not finite; n_clouds < 0, n < 0
+ * and the offset errors of athena_mp_farthest_points, in its wording; an origin that is not finite; a non-finite coordinate (cloud,
+ * component and point of the first one are named, 1-based); hi_k - lo_k not finite (cloud and axis named); an origin above a
+ * coordinate (cloud, axis and the cloud's first such point named); nc_k > 2^21 on an axis (cloud and axis named);
+ * bits_for(n_clouds - 1) + bits_for(max N_b - 1) > 62, bits_for(v) = the bits of v, at least 1; capacity < m with a device output
+ * given.  There is no other limit on the number of cells.  n == 0 or n_clouds == 0 succeeds with no clusters.  The library stays
+ * usable after a refusal.  Two calls on the same input are byte-identical.  Cost: a cluster is summed by one group of 4 lanes in member order;
+ * a cluster of many thousands of points is that group's loop. */
+int athena_mp_grid_clusters(int32_t n_clouds, int32_t n, const int32_t *offsets_host, int32_t dim, const float *points_dev, float size,
+                            const float *origin_host, int64_t capacity, int32_t *cluster_dev, int32_t *pairs_dev, int32_t *rowptr_dev,
+                            float *weights_dev, float *centroid_dev, int32_t *nearest_dev, int32_t *cell_dev,
+                            int32_t *cluster_offsets_host, float *origin_out_host, int64_t *n_clusters_out);
+/* The reverse step of centroid: dpoints[j, k] = dcentroid[c, k] / fl(count_c), c = cluster[j], count_c = rowptr[c + 1] - rowptr[c]
+ * (only differences of rowptr are used: a 1-based adj_ia serves as well); fp32, / correctly rounded: every bit is defined.  lo is a
+ * constant and cancels; nearest and cell carry no gradient.  cluster [n], rowptr [n_clusters + 1], dcentroid [n_clusters, dim] and
+ * dpoints [n, dim] on the device.  Refused with a message: dim outside 1..3, a negative count, a cluster id outside 1..n_clusters
+ * (the first such point is named; nothing is read through it). */
+int athena_mp_grid_clusters_grad(int32_t n, int32_t dim, int32_t n_clusters, const int32_t *cluster_dev, const int32_t *rowptr_dev,
+                                 const float *dcentroid_dev, float *dpoints_dev);
+/* athena_mp_grid_clusters with every array on the host, for callers that hold Fortran arrays: the membership as adj_ia
+ * [capacity + 1] (1-based) and adj_ja [2, n] column-major (point, edge id: pair e is entry e) in the conventions of
+ * athena_mp_radius_graph_bipartite_host; cluster, weights [n], centroid, cell [capacity, dim] and nearest [capacity] may each be
+ * NULL.  adj_ja_out == NULL: size query for *n_clusters_out, cluster_offsets and origin_out. */
+int athena_mp_grid_clusters_host(int32_t n_clouds, int32_t n, const int32_t *offsets_host, int32_t dim, const float *points_host,
+                                 float size, const float *origin_host, int64_t capacity, int32_t *cluster_out, int32_t *adj_ia_out,
+                                 int32_t *adj_ja_out, float *weights_out, float *centroid_out, int32_t *nearest_out, int32_t *cell_out,
+                                 int32_t *cluster_offsets_out, float *origin_out, int64_t *n_clusters_out);
+/* athena_mp_grid_clusters_grad with every array on the host, staged through HBM. */
+int athena_mp_grid_clusters_grad_host(int32_t n, int32_t dim, int32_t n_clusters, const int32_t *cluster, const int32_t *rowptr,
+                                      const float *dcentroid, float *dpoints);
+/* What the last athena_mp_grid_clusters call did: out[0] = clusters, out[1] = the key bits sorted (cloud bits + cell bits), out[2] =
+ * the 8-bit passes of the radix sort, out[3] = the members of the largest cluster (0 after a size query). */
+int athena_mp_grid_clusters_stats(int64_t out[4]);
 /* Periodic structures -> neighbour graphs on the device, a batch per call (periodic_graph.hip).  It replaces get_graph_from_basis
  * of the reference's chemical examples (example/example_library/src/mod_read_chemical_graphs.f90:196-278); the step in front of
  * athena_mp_graph_create_from_edges_dev.
