@@ -9,6 +9,6 @@ from .graph import DeviceGraph, duvenaud_plan_stats, graph_type  # noqa: F401
 from . import geometry  # noqa: F401
 from .geometry import points_grad, structures_grad, structures_grad_host  # noqa: F401
 from . import batching  # noqa: F401
-from .batching import Batch, DeviceDataset  # noqa: F401
+from .batching import Batch, Block, DeviceDataset, NeighborSampler  # noqa: F401
 
-__all__ = ["_capi", "DeviceGraph", "duvenaud_plan_stats", "graph_type", "geometry", "points_grad", "structures_grad", "structures_grad_host", "batching", "Batch", "DeviceDataset"]
+__all__ = ["_capi", "DeviceGraph", "duvenaud_plan_stats", "graph_type", "geometry", "points_grad", "structures_grad", "structures_grad_host", "batching", "Batch", "DeviceDataset", "Block", "NeighborSampler"]

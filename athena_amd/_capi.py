@@ -98,6 +98,14 @@ _PROTOS = {
     "athena_mp_batch_plan_create": [_vp, _i32, _vp, _vp, C.POINTER(_vp)],
     "athena_mp_batch_plan_destroy": [_vp],
     "athena_mp_batch_select": [_vp, _i32, _vp, C.POINTER(_vp), _vp, _vp, _vp, _vp],
+    "athena_mp_sampler_create": [_vp, C.POINTER(_vp)],
+    "athena_mp_sampler_destroy": [_vp],
+    "athena_mp_sample_count": [_vp, _i32, _vp, _i32, _vp, C.POINTER(_i64)],
+    "athena_mp_sample_neighbors": [_vp, _i32, _vp, _i32, C.c_uint64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, C.POINTER(_i32), C.POINTER(_i64),
+                                   C.POINTER(_vp)],
+    "athena_mp_sample_neighbors_host": [_vp, _i32, _vp, _i32, C.c_uint64, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i32),
+                                        C.POINTER(_i64), C.POINTER(_vp)],
+    "athena_mp_sample_stats": [_vp],
     "athena_mp_duvenaud_plan": [_vp, _i32, _i32],
     "athena_mp_duvenaud_plan_export": [_vp, _i32, _vp, _i64, _vp],
     "athena_mp_duvenaud_plan_stats": [C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)],

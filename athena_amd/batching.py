@@ -9,6 +9,16 @@ batch on the host and without searching its neighbours again.
         out = layer.forward(b.take_vertices(x), b.take_edges(feature)[:, None]) ...
         g = structures_grad(b.handle, b.take_structures(lat), b.vertex_offsets, b.edge_offsets, b.take_edges(vec), cutoff_max, dfeature=de)
 
+ONE large graph (a citation or product graph, a mesh, a point cloud joined by from_points_knn) is not a dataset of structures:
+NeighborSampler draws neighbour-sampled mini-batches of its vertices instead (athena_amd/csrc/neighbor_sample.hip).
+
+    sampler = NeighborSampler(handle)                                          # once
+    for blocks in sampler.batches(1024, (10, 10), seed=epoch):                 # outermost block first
+        h = blocks[0].take_vertices(x)
+        for layer, b in zip(layers, blocks):
+            layer.set_graph_handle(b.handle)
+            h = layer.forward(h) ...                                           # [b.handle.n_cols, F] -> [b.n_seeds, F]
+
 A batch's handle is a deep copy: it outlives the dataset and is closed like any DeviceGraph.  Gradients come back in batch order (a
 batch's forces are compared with the batch's gathered targets); scattering them to dataset order is not part of this module."""
 import ctypes as C
@@ -152,6 +162,152 @@ class DeviceDataset:
         """destroys the plan; the dataset handle is the caller's, batches already drawn stay valid"""
         if getattr(self, "_plan", None):
             _capi.load().athena_mp_batch_plan_destroy(self._plan)
+            self._plan = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+_HOP = 0xD1B54A32D192ED03
+_DEGREES = {"block": 0, "parent": 1}
+
+
+class Block:
+    """One hop of a NeighborSampler: handle (a DeviceGraph that owns the rectangular block: row s is seed s, its columns are the seeds
+    first, then the other sampled vertices ascending by id), n_seeds, and the int32 device tensors vertex_map [n_cols] (the parent
+    vertex of every column; vertex_map[:n_seeds] are the seeds), entry_map [nnz] (the parent CSR position of every entry) and
+    edge_map [nnz] (the parent edge column of every entry, -1 for an entry without one; None when the parent has no edge columns).
+    All three are 0-based, as Batch.vertex_map: the C ABI's are 1-based, like `sample` of geometry.farthest_points."""
+
+    def __init__(self, handle, n_seeds, vertex_map, entry_map, edge_map, parent_rows, vertex_ids):
+        self.handle, self.n_seeds = handle, n_seeds
+        self.vertex_map, self.entry_map, self.edge_map = vertex_map, entry_map, edge_map
+        self._rows = parent_rows                                               # the parent's (vertices, edge columns, entries)
+        self._vertex_ids = vertex_ids                                          # vertex_map 1-based: the next hop's seeds as they are
+
+    def take_vertices(self, t):
+        """the block's columns of a per-vertex tensor of the parent, [n, ...] -> [n_cols, ...]; its first n_seeds rows are the seeds'"""
+        return Batch._take(t, self.vertex_map, self._rows[0], "take_vertices")
+
+    def take_edges(self, t):
+        """the block's entries of a per-edge tensor of the parent (feature [E], coords [E, 3], ...), one row per entry, which is the
+        block's edge column; an entry without an edge column (edge_map < 0) takes row 0"""
+        if self.edge_map is None:
+            raise ValueError("take_edges: the parent has no edge columns")
+        return Batch._take(t, self.edge_map.clamp(min=0), self._rows[1], "take_edges")
+
+    def take_entries(self, t):
+        """the block's entries of a per-entry tensor of the parent (one row per CSR position), [nnz_parent, ...] -> [nnz, ...]"""
+        return Batch._take(t, self.entry_map, self._rows[2], "take_entries")
+
+    def close(self):
+        self.handle.close()
+
+
+class NeighborSampler:
+    """Neighbour-sampled mini-batches of one square handle that stays on the device (athena_mp_sampler_create; the definition is in
+    include/athena_mp.h).  Owns the sampler plan and keeps the handle alive; one sample at a time."""
+
+    def __init__(self, handle):
+        if handle.n_rows != handle.n_cols:
+            raise ValueError(f"a rectangular handle ({handle.n_rows} x {handle.n_cols}) has no vertices to walk on")
+        self.handle = handle
+        self.num_vertices = int(handle.n_rows)
+        _capi.use_torch_stream()
+        plan = C.c_void_p()
+        _capi.call("athena_mp_sampler_create", handle.handle, C.byref(plan))
+        self._plan = plan
+        self.hop_stats = []                                                    # stats() of every hop of the last sample()
+
+    def __len__(self):
+        return self.num_vertices
+
+    def _hop(self, seeds1, k, seed, mode):
+        import torch
+
+        dev = seeds1.device
+        m, n = int(seeds1.numel()), self.num_vertices
+        _capi.use_torch_stream()
+        if k > 0:
+            cap = m * k                                                        # rows have min(L, k) entries
+        else:
+            nnz = C.c_int64()
+            _capi.call("athena_mp_sample_count", self._plan, m, C.c_void_p(seeds1.data_ptr()), k, None, C.byref(nnz))
+            cap = nnz.value
+        vcap = min(n, m + cap)
+        has_edges = self.handle.n_edge_cols > 0
+        vm = torch.empty(vcap, dtype=torch.int32, device=dev)
+        em = torch.empty(cap, dtype=torch.int32, device=dev)
+        ed = torch.empty(cap, dtype=torch.int32, device=dev) if has_edges else None
+        n_cols, nnz, block = C.c_int32(), C.c_int64(), C.c_void_p()
+        _capi.call("athena_mp_sample_neighbors", self._plan, m, C.c_void_p(seeds1.data_ptr()), k, C.c_uint64(seed), mode,
+                   C.c_void_p(vm.data_ptr()), vcap, C.c_void_p(em.data_ptr()), cap, C.c_void_p(ed.data_ptr()) if has_edges else None, cap,
+                   C.byref(n_cols), C.byref(nnz), C.byref(block))
+        g = DeviceGraph.borrow(block)
+        g._borrowed = False                                                    # the block owns its handle: close() destroys it
+        vm = vm[:n_cols.value]
+        rows = (n, self.handle.n_edge_cols, int(self.handle.nnz))
+        return Block(g, m, vm - 1, em[:nnz.value].sub_(1), ed[:nnz.value].sub_(1) if has_edges else None, rows, vm)
+
+    def sample(self, seeds, fanouts, seed=0, degrees="block"):
+        """The blocks of the vertices `seeds` (0-based, distinct, any order: a sequence, a numpy array or an int32 device tensor), one
+        per fan-out: hop h draws fanouts[h] entries per row, hop 0 around the seeds, each further hop around the previous hop's whole
+        vertex_map.  A fan-out is 1..64, or 0 for every entry.  Returned outermost first, the order the layers apply them: blocks[0] is
+        fed with blocks[0].take_vertices(x), blocks[-1] has the seeds as its rows, and blocks[i].vertex_map[:blocks[i].n_seeds] equals
+        blocks[i + 1].vertex_map.  degrees: "block" (row lengths and column counts of the block) or "parent" (the parent's degrees
+        of the same vertices: with fan-out 0 a Kipf step on the block is the parent's step on the seed rows).  The same (seed, vertex)
+        draws the same neighbours whatever else is in the batch; pass the epoch as the seed."""
+        import torch
+
+        if self._plan is None:
+            raise ValueError("the sampler is closed")
+        if degrees not in _DEGREES:
+            raise ValueError('degrees must be "block" or "parent"')
+        fanouts = [int(k) for k in fanouts]
+        if not fanouts or any(k < 0 or k > 64 for k in fanouts):
+            raise ValueError("fanouts: at least one, each in 0..64 (0: every entry)")
+        dev = torch.device("cuda", torch.cuda.current_device())
+        if isinstance(seeds, torch.Tensor):
+            s1 = seeds.to(dev, torch.int32).reshape(-1) + 1
+        else:
+            s1 = torch.from_numpy(np.ascontiguousarray(seeds, dtype=np.int32).reshape(-1) + np.int32(1)).to(dev)
+        blocks, self.hop_stats = [], []
+        for h, k in enumerate(fanouts):
+            b = self._hop(s1, k, (int(seed) + _HOP * (h + 1)) % 2 ** 64, _DEGREES[degrees])
+            blocks.append(b)
+            self.hop_stats.append(self.stats())                               # per hop, in hop order
+            s1 = b._vertex_ids
+        return blocks[::-1]
+
+    def batches(self, batch_size, fanouts, ids=None, shuffle=True, seed=0, drop_last=False):
+        """The block lists of one epoch, batch_size seed vertices each (the last one smaller unless drop_last), over the vertices `ids`
+        (None: all of them).  With shuffle the order is numpy.random.default_rng(seed).permutation, as DeviceDataset.batches: pass
+        the epoch as the seed for a new order and new neighbours every epoch."""
+        batch_size = int(batch_size)
+        if batch_size < 1:
+            raise ValueError("batch_size must be at least 1")
+        ids = np.arange(self.num_vertices, dtype=np.int32) if ids is None else np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        order = ids[np.random.default_rng(seed).permutation(ids.size)] if shuffle else ids
+        for i0 in range(0, order.size, batch_size):
+            part = order[i0:i0 + batch_size]
+            if drop_last and part.size < batch_size:
+                break
+            yield self.sample(part, fanouts, seed=seed)
+
+    def stats(self):
+        """of the last hop sampled: rows drawn by key, rows copied whole, 64-entry steps, steps skipped, and the microseconds of the
+        count stretch, the draw kernel, the relabelling and the handle (athena_mp_sample_stats)"""
+        out = np.zeros(8, np.int64)
+        _capi.call("athena_mp_sample_stats", out.ctypes.data_as(C.c_void_p))
+        return out
+
+    def close(self):
+        """destroys the plan; the parent handle is the caller's, blocks already drawn stay valid"""
+        if getattr(self, "_plan", None):
+            _capi.load().athena_mp_sampler_destroy(self._plan)
             self._plan = None
 
     def __del__(self):

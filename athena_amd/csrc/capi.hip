@@ -460,6 +460,15 @@ static int graph_create_impl(int32_t n_rows, int32_t n_cols, int64_t nnz, const 
     return rc;
 }
 
+extern "C++" {
+/* graph_create for a CSR whose entries (column, edge id) [2, nnz] are already in HBM: neighbor_sample.hip */
+int amp::graph_create_dev(int32_t n_rows, int32_t n_cols, int64_t nnz, const int32_t *adj_ia, const int32_t *adj_ja_dev,
+                          int32_t n_edge_cols, const int32_t *row_deg, const int32_t *col_deg, athena_mp_graph **out)
+{
+    return graph_create_impl(n_rows, n_cols, nnz, adj_ia, nullptr, adj_ja_dev, n_edge_cols, row_deg, col_deg, out);
+}
+}   // extern "C++"
+
 /* ---- content key of a CSR (what a cached handle is valid for) ------------------------------------------------- */
 namespace {
 struct KeyHash {   // MurmurHash3's 64-bit lane: multiply-rotate per 8-byte word, fmix64 at the end

@@ -170,6 +170,9 @@ int csr_from_edges_core(int32_t n_vertices, int64_t n_pairs, const int32_t *inde
 int bipartite_csr_from_pairs(const char *who, int32_t n_rows, int32_t n_cols, int64_t n_pairs, const int32_t *pairs_dev,
                              int32_t *adj_ia_out, int32_t *adj_ja_out, int64_t capacity, int32_t **ja_dev, std::vector<int32_t> *row_deg,
                              std::vector<int32_t> *col_deg);
+// athena_mp_graph_create for a CSR whose entries (column, edge id) [2, nnz] lie in HBM; adj_ia and the degrees on the host (capi.hip)
+int graph_create_dev(int32_t n_rows, int32_t n_cols, int64_t nnz, const int32_t *adj_ia, const int32_t *adj_ja_dev, int32_t n_edge_cols,
+                     const int32_t *row_deg, const int32_t *col_deg, athena_mp_graph **out);
 // The end of a point-cloud *_graph_host entry (radius_graph.hip, knn_graph.hip) once the pair count E is known: the sizes out,
 // the size query's return, the capacity checks, then pairs(&d_pairs, &d_coords) -- the E pairs [2, E] and coords [E, dim] on the
 // device, built or already there -- the coords home and the CSR through csr_from_edges_core.

@@ -69,6 +69,8 @@ module athena_mp_c
   public :: athena_mp_edge_grad_to_points_host, athena_mp_periodic_grad_host
   public :: athena_mp_batch_plan_create, athena_mp_batch_plan_destroy, athena_mp_batch_select
   public :: athena_mp_duvenaud_plan, athena_mp_duvenaud_plan_export, athena_mp_duvenaud_plan_stats
+  public :: athena_mp_sampler_create, athena_mp_sampler_destroy, athena_mp_sample_count, athena_mp_sample_neighbors
+  public :: athena_mp_sample_neighbors_host, athena_mp_sample_stats
   public :: athena_mp_error_message
   public :: athena_mp_pull_gemm, athena_mp_dev_offset, athena_mp_kipf_layer_bwd
   public :: athena_mp_comm_create, athena_mp_comm_create_from_file, athena_mp_comm_destroy, athena_mp_comm_barrier
@@ -992,6 +994,55 @@ module athena_mp_c
        type(c_ptr), value :: plan, child, offsets_out, edge_offsets_out, vertex_map_dev, edge_map_dev
        integer(c_int32_t), value :: n_sel
        integer(c_int32_t), intent(in) :: sel(*)
+     end function
+     !! Neighbour-sampled mini-batches of ONE large graph (definition: include/athena_mp.h).  The sampler plan borrows the parent
+     !! handle (n_rows == n_cols) and must be destroyed before it.  Every id is 1-based.
+     integer(c_int) function athena_mp_sampler_create(parent, sampler) bind(C, name="athena_mp_sampler_create")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: parent
+       type(c_ptr), intent(out) :: sampler
+     end function
+     integer(c_int) function athena_mp_sampler_destroy(sampler) bind(C, name="athena_mp_sampler_destroy")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: sampler
+     end function
+     !! the count pass alone: seeds_dev (n_seeds) a device pointer, rowptr_dev (n_seeds + 1, 0-based) a device pointer or c_null_ptr
+     integer(c_int) function athena_mp_sample_count(sampler, n_seeds, seeds_dev, k, rowptr_dev, nnz) bind(C, name="athena_mp_sample_count")
+       import :: c_int, c_int32_t, c_int64_t, c_ptr
+       type(c_ptr), value :: sampler, seeds_dev, rowptr_dev
+       integer(c_int32_t), value :: n_seeds, k
+       integer(c_int64_t), intent(out) :: nnz
+     end function
+     !! one hop on device arrays: the three maps are device pointers with their capacities in elements, each may be c_null_ptr;
+     !! block = c_loc of a type(c_ptr), target variable that receives the handle, or c_null_ptr.  degree_mode 0 = block, 1 = parent
+     integer(c_int) function athena_mp_sample_neighbors(sampler, n_seeds, seeds_dev, k, seed, degree_mode, vertex_map_dev, &
+          vertex_capacity, entry_map_dev, entry_capacity, edge_map_dev, edge_capacity, n_cols, nnz, block) &
+          bind(C, name="athena_mp_sample_neighbors")
+       import :: c_int, c_int32_t, c_int64_t, c_ptr
+       type(c_ptr), value :: sampler, seeds_dev, vertex_map_dev, entry_map_dev, edge_map_dev, block
+       integer(c_int32_t), value :: n_seeds, k, degree_mode
+       integer(c_int64_t), value :: seed, vertex_capacity, entry_capacity, edge_capacity
+       integer(c_int32_t), intent(out) :: n_cols
+       integer(c_int64_t), intent(out) :: nnz
+     end function
+     !! one hop on Fortran arrays: seeds (n_seeds); vertex_map (vertex_capacity), entry_map, edge_map (entry_capacity), adj_ia
+     !! (n_seeds + 1) and adj_ja (2, entry_capacity) as c_loc of host arrays, the maps each may be c_null_ptr; adj_ja = c_null_ptr
+     !! is the size query for n_cols and nnz.  seed: the 64 bits of the definition's unsigned seed
+     integer(c_int) function athena_mp_sample_neighbors_host(sampler, n_seeds, seeds, k, seed, degree_mode, vertex_capacity, &
+          entry_capacity, vertex_map, entry_map, edge_map, adj_ia, adj_ja, n_cols, nnz, block) &
+          bind(C, name="athena_mp_sample_neighbors_host")
+       import :: c_int, c_int32_t, c_int64_t, c_ptr
+       type(c_ptr), value :: sampler, vertex_map, entry_map, edge_map, adj_ia, adj_ja, block
+       integer(c_int32_t), value :: n_seeds, k, degree_mode
+       integer(c_int32_t), intent(in) :: seeds(*)
+       integer(c_int64_t), value :: seed, vertex_capacity, entry_capacity
+       integer(c_int32_t), intent(out) :: n_cols
+       integer(c_int64_t), intent(out) :: nnz
+     end function
+     !! of the last sample: rows drawn, rows copied whole, steps, steps skipped, then four times in microseconds
+     integer(c_int) function athena_mp_sample_stats(stats) bind(C, name="athena_mp_sample_stats")
+       import :: c_int, c_int64_t
+       integer(c_int64_t), intent(out) :: stats(8)
      end function
      !! the Duvenaud degree-bucket plan of a handle (definition: include/athena_mp.h): built now, on the library's stream; a no-op
      !! when the handle already holds the plan of (min_deg, max_deg).  Called right after athena_mp_batch_select on the child

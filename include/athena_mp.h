@@ -694,6 +694,68 @@ int athena_mp_batch_plan_create(const athena_mp_graph *g, int32_t n_structures, 
 int athena_mp_batch_plan_destroy(athena_mp_batch_plan *p);
 int athena_mp_batch_select(const athena_mp_batch_plan *p, int32_t n_sel, const int32_t *sel_host, athena_mp_graph **out,
                            int32_t *offsets_out, int64_t *edge_offsets_out, int32_t *vertex_map_dev, int32_t *edge_map_dev);
+/* Neighbour-sampled mini-batches of ONE large graph that stays in HBM (neighbor_sample.hip): seeds -> a sampled rectangular block
+ * per hop, relabelled, as a handle the Kipf, Duvenaud and graph_nop(local_term = false) steps take as it is.  athena_mp_batch_select
+ * draws whole structures out of a block-diagonal dataset; this draws rows out of a graph that is one piece (a citation or product
+ * graph, a mesh, a LIDAR sweep joined by athena_mp_knn_pairs).  Integer only: every implementation gives the same arrays, two calls
+ * on the same input are byte-identical.  Ids are 1-based on this side of the boundary, as `sample` of athena_mp_farthest_points.
+ *   Parent: any handle with n_rows == n_cols = n (self loops and multigraphs allowed, with or without edge columns).  A sampler
+ *   plan borrows it (the parent must outlive the plan) and owns one int32 slot[n] in HBM, all -1 between calls, and reusable
+ *   scratch.  One sample at a time per plan, ordered on the library's stream.
+ *   A hop takes seeds [m] (distinct vertices, 1-based, on the device), a fan-out 1 <= k <= 64 or 0 for every entry, a 64-bit seed
+ *   and a degree mode (0 = block, 1 = parent).
+ *   Key of the entry at position p = w - rowptr[r] of the row of seed vertex r (0-based global row), all arithmetic mod 2^64:
+ *       z = seed + 0x9E3779B97F4A7C15 * (((r << 32) | p) + 1)
+ *       z ^= z >> 30;  z *= 0xBF58476D1CE4E5B9;  z ^= z >> 27;  z *= 0x94D049BB133111EB;  z ^= z >> 31
+ *       key = (z & 0xFFFFFFFF00000000) | p
+ *   Selection: a row of length L <= k (or k = 0) is taken whole; otherwise the k entries with the smallest keys.  Chosen entries
+ *   keep the parent's CSR order (ascending p).  So row s of the block has min(L, k) entries, rowptr is known before anything is
+ *   drawn, and A VERTEX'S SAMPLE DEPENDS ON (seed, r) ALONE, not on which other seeds share the batch.  Entries, not neighbours,
+ *   are drawn: a duplicated entry of a multigraph can be chosen twice.
+ *   Relabelling: the block has n_rows = m; its columns are the seeds first in the order given (local id = position), then every
+ *   other vertex that occurs as a chosen column, ascending by global id.  vertex_map [n_cols] = the global ids (vertex_map[:m] are
+ *   the seeds); entry_map [nnz] = the parent CSR position w (1-based) of each block entry.  A parent with edge columns gives a block
+ *   with one edge column per entry (edge id = entry index, what the interpolation, pooling and edge-gather entries require) and
+ *   edge_map [nnz] = the parent's edge column of that entry, 1-based, 0 for an entry without one; a parent without edge columns
+ *   gives a block without, and edge_map is not written.
+ *   Degrees: block (0) = the row lengths and the number of block entries in each column, what athena_mp_graph_create_bipartite_dev
+ *   would give; parent (1) = the parent's deg_row[seed] and deg_col[vertex_map].  With k = 0 and parent degrees a Kipf step on the
+ *   block reproduces the parent's step on the seed rows.
+ *   The handle is, array for array (all thirteen of athena_mp_graph_export), what athena_mp_graph_create(m, n_cols, nnz, adj_ia,
+ *   adj_ja, n_edge_cols, row_deg, col_deg) builds from the block's CSR with those degrees (it IS that builder, fed from HBM); never
+ *   in the handle cache, freed by athena_mp_graph_destroy, valid after the plan and the parent are gone.
+ *   Several hops are several calls: hop h (0-based) uses seed_h = seed + 0xD1B54A32D192ED03 * (h + 1) mod 2^64, so a vertex is not
+ *   handed the same neighbours twice, and its seeds are hop h - 1's whole vertex_map (the device array as it is).  The layers apply
+ *   the blocks outermost first: outer.vertex_map[:outer.n_rows] == inner.vertex_map.
+ * athena_mp_sample_count: the count pass alone, nnz of the block these seeds and k give (n_cols <= m + nnz); rowptr_dev [m + 1]
+ *   (0-based, may be NULL) receives the block's row pointer.
+ * athena_mp_sample_neighbors: vertex_map_dev / entry_map_dev / edge_map_dev are the caller's device buffers with their capacities in
+ *   elements, each may be NULL (4-byte alignment is all they need); *n_cols_out and *nnz_out are always set on success; block may be
+ *   NULL (the maps alone).  After a capacity refusal the buffers' contents are undefined.  A hop makes three host waits of its own
+ *   (nnz and the seed flags; the number of new columns; the column degrees) in front of those of the handle's builder.
+ * athena_mp_sample_neighbors_host: seeds and every output on the host (Fortran arrays), staged through HBM; also returns the block's
+ *   CSR as adj_ia [m + 1] and adj_ja [2, entry_capacity] (column, edge id; 1-based, edge id 0 without edge columns).  The maps may
+ *   each be NULL; block may be NULL.  adj_ja_out == NULL: size query for *n_cols_out and *nnz_out.
+ * athena_mp_sample_stats, of the last sample: out[0] = rows drawn by key, out[1] = rows copied whole, out[2] = 64-entry steps of the
+ *   drawn rows, out[3] = the steps skipped because no key lay below the current k-th; out[4..7] = microseconds of the count stretch
+ *   (host clock, with its wait), the draw kernel, the relabelling (both device events) and the handle (host clock).
+ * Refused with a message: n_rows != n_cols; k outside 0..64; a degree mode other than 0 or 1; a seed outside [1, n] (the first one
+ * is named); a repeated seed (the first repetition is named); a capacity too small (the buffer is named); nnz or n_cols >= 2^31.
+ * The library stays usable after a refusal, slot is put back, and the next sample is correct. */
+typedef struct athena_mp_sampler athena_mp_sampler;
+int athena_mp_sampler_create(const athena_mp_graph *parent, athena_mp_sampler **out);
+int athena_mp_sampler_destroy(athena_mp_sampler *p);
+int athena_mp_sample_count(athena_mp_sampler *p, int32_t n_seeds, const int32_t *seeds_dev, int32_t k, int32_t *rowptr_dev,
+                           int64_t *nnz_out);
+int athena_mp_sample_neighbors(athena_mp_sampler *p, int32_t n_seeds, const int32_t *seeds_dev, int32_t k, uint64_t seed,
+                               int32_t degree_mode, int32_t *vertex_map_dev, int64_t vertex_capacity, int32_t *entry_map_dev,
+                               int64_t entry_capacity, int32_t *edge_map_dev, int64_t edge_capacity, int32_t *n_cols_out,
+                               int64_t *nnz_out, athena_mp_graph **block);
+int athena_mp_sample_neighbors_host(athena_mp_sampler *p, int32_t n_seeds, const int32_t *seeds_host, int32_t k, uint64_t seed,
+                                    int32_t degree_mode, int64_t vertex_capacity, int64_t entry_capacity, int32_t *vertex_map_out,
+                                    int32_t *entry_map_out, int32_t *edge_map_out, int32_t *adj_ia_out, int32_t *adj_ja_out,
+                                    int32_t *n_cols_out, int64_t *nnz_out, athena_mp_graph **block);
+int athena_mp_sample_stats(int64_t out[8]);
 
 /* The Duvenaud degree-bucket plan of a handle (bucket_plan.hip): what the bucketed update kernels (duv_mfma.hip) read.  A layer call
  * builds it on first use for its (min_deg, max_deg); athena_mp_duvenaud_plan builds it NOW, on the library's stream -- a training loop
