@@ -26,8 +26,11 @@ namespace {
 typedef float v4f __attribute__((ext_vector_type(4)));
 
 // Epilogue arithmetic is kept off the critical path of the matrix pipe: the sigmoid uses the hardware
-// exp2 / rcp (each 1 ulp; the result is within ~4e-7 relative of the libm form, inside the 1e-5 bound the
-// MFMA route is tested to), and x/d for the bucket divisor d uses one Newton correction on x*(1/d):
+// exp2 / rcp (each 1 ulp).  The exponent's argument x * fl(-log2(e) * fl(1/d)) is rounded about 2.5 times, and one
+// rounding of it moves exp by |t| 2^-24 relative (t = x/d), so the result's distance from the libm form GROWS with
+// |t|: measured <= 1.3 |t| 2^-24 -- 5e-7 below |t| = 8, 1.8e-6 below 32, 3.8e-6 at 80 .. 87, where the libm form stays
+// at 1e-7 (the fused readout softmax the same, in |logit - max|).  tests/test_gpu_activation_edges.py holds both to
+// 1e-5 max(1, |t|/32) per element.  x/d for the bucket divisor d uses one Newton correction on x*(1/d):
 // 3 instructions instead of the ~10 of the IEEE division sequence, equal to the IEEE quotient in all but
 // ~4 of 1e5 operands and 1 ulp off otherwise (checked exhaustively-by-sampling for d = 1..64).
 __device__ __forceinline__ float act_apply(float t, int act)

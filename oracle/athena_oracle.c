@@ -603,8 +603,11 @@ float oracle_mse(size_t n, const float *pred, const float *expected, float *dpre
 
 /* swish_array / get_partial_swish_val    athena_diffstruc_extd_sub.f90:424-455, :477-492
  *   y = x * (1 / (1 + exp(-beta*x)));  dx = g * e * (beta*x + e + 1) / (e + 1)**2, e = exp(beta*x)
- *   (the reverse pass differentiates at the INPUT x, and overflows to inf/inf = NaN exactly where
- *   the reference does, beta*x > ~88) */
+ *   (the reverse pass differentiates at the INPUT x, and overflows exactly where the reference does: (e + 1)**2
+ *   and e * (beta*x + e + 1) pass FLT_MAX together once e*e does, at beta*x = 44.36, not where e itself overflows
+ *   (~88).  With |g| >= 1 the factor is finite up to beta*x = 44 and inf/inf = NaN from 45 on; with a smaller |g| the
+ *   numerator stays finite a little longer and the factor is finite/inf = 0 in between.
+ *   tests/test_activation_reference.py pins this) */
 void oracle_swish(size_t n, float beta, const float *x, float *y)
 {
     for (size_t i = 0; i < n; ++i) y[i] = x[i] * (1.0f / (1.0f + expf(-beta * x[i])));
