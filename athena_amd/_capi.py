@@ -84,6 +84,15 @@ _PROTOS = {
     "athena_mp_pool_max_bwd_edges": [_vp, _i32, _vp, _vp, _vp],
     "athena_mp_pool_max_host": [_vp, _i32, _vp, _vp, _vp, _vp],
     "athena_mp_pool_max_bwd_host": [_vp, _i32, _vp, _vp, _vp, _vp],
+    "athena_mp_attn_softmax_fwd": [_vp, _i32, _vp, _vp],
+    "athena_mp_attn_gather_fwd": [_vp, _i32, _i32, _vp, _vp, _vp],
+    "athena_mp_attn_gather_edges_fwd": [_vp, _i32, _i32, _vp, _vp, _vp],
+    "athena_mp_attn_gather_bwd_x": [_vp, _i32, _i32, _vp, _vp, _vp],
+    "athena_mp_attn_gather_bwd_edges": [_vp, _i32, _i32, _vp, _vp, _vp],
+    "athena_mp_attn_gather_bwd_alpha": [_vp, _i32, _i32, _vp, _vp, _vp, _vp],
+    "athena_mp_attn_softmax_bwd": [_vp, _i32, _vp, _vp, _vp],
+    "athena_mp_attention_host": [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp],
+    "athena_mp_attention_bwd_host": [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "athena_mp_edge_gather_fwd": [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _vp],
     "athena_mp_edge_gather_bwd": [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp],
     "athena_mp_edge_gather_host": [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _vp],

@@ -214,6 +214,8 @@ int edge_form_check(const char *who, const athena_mp_graph *g);
 int interp_check(const char *who, const athena_mp_graph *g, const int32_t *dim, const int32_t *F, const float *eps);
 // argument checks of the max-pooling entries (pool.hip), shared with their *_host forms; the edge forms add edge_form_check
 int pool_check(const char *who, const athena_mp_graph *g, int32_t F, bool edge_form);
+// argument checks of the attention entries (attention.hip), shared with their *_host forms: edge_form_check, then H, F and F % H
+int attn_check(const char *who, const athena_mp_graph *g, int32_t F, int32_t H);
 // argument checks of the edge-gather entries (edge_gather.hip), shared with their *_host forms: edge_form_check, then the widths
 int edge_gather_check(const char *who, const athena_mp_graph *g, int32_t Fs, int32_t Fq, int32_t dim, int32_t relative, int32_t ld);
 void graph_cache_clear(); // idle and live handles of athena_mp_graph_acquire (capi.hip)

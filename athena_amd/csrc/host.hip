@@ -732,6 +732,50 @@ int athena_mp_pool_max_bwd_host(const athena_mp_graph *g, int32_t F, const int32
                       return dh ? athena_mp_pool_max_bwd_edges(g, F, (int32_t *)p[0], (float *)p[1], (float *)p[3]) : 0;
                   });
 }
+// ---- attention pooling (attention.hip): the softmax, then the gather of either form; the reverse steps that were asked for -------
+int athena_mp_attention_host(const athena_mp_graph *g, int32_t F, int32_t H, const float *scores, const float *x, const float *h,
+                             float *alpha, float *y)
+{
+    AMP_REQUIRE((x != nullptr) != (h != nullptr), "attention_host: exactly one of x (the vertex form) and h (the edge form) must be given");
+    const bool edges = h != nullptr;
+    if (int rc = attn_check("attention_host", g, F, H)) return rc;
+    const int64_t E = g->n_edge_cols;
+    AMP_REQUIRE((E == 0 || scores) && (g->n_rows == 0 || y), "attention_host: null array");
+    // alpha lives in HBM whether the caller wants it or not: an absent output is a buffer that goes nowhere
+    return staged({{scores, nullptr, fb(E, H)}, {edges ? h : x, nullptr, fb(edges ? E : g->n_cols, F)}, {nullptr, alpha, fb(E, H)},
+                   {nullptr, y, fb(g->n_rows, F)}},
+                  [&](std::vector<void *> &p) {
+                      if (int rc = athena_mp_attn_softmax_fwd(g, H, (float *)p[0], (float *)p[2])) return rc;
+                      return edges ? athena_mp_attn_gather_edges_fwd(g, F, H, (float *)p[2], (float *)p[1], (float *)p[3])
+                                   : athena_mp_attn_gather_fwd(g, F, H, (float *)p[2], (float *)p[1], (float *)p[3]);
+                  });
+}
+int athena_mp_attention_bwd_host(const athena_mp_graph *g, int32_t F, int32_t H, const float *alpha, const float *x, const float *h,
+                                 const float *dy, float *dx, float *dh, float *dscores)
+{
+    AMP_REQUIRE(dx || dh || dscores, "attention_bwd_host: dx, dh and dscores are all null: nothing to compute");
+    if (int rc = attn_check("attention_bwd_host", g, F, H)) return rc;
+    AMP_REQUIRE(!dscores || (x != nullptr) != (h != nullptr),
+                "attention_bwd_host: dscores needs exactly one of x (the vertex form) and h (the edge form)");
+    const int64_t E = g->n_edge_cols;
+    AMP_REQUIRE(E == 0 || (alpha && dy), "attention_bwd_host: null array");
+    auto in = [](const float *host, size_t bytes) { return Stage{host, nullptr, host ? bytes : 0}; };
+    auto out = [](float *host, size_t bytes) { return Stage{nullptr, host, host ? bytes : 0, true}; };
+    return staged({{alpha, nullptr, fb(E, H)}, in(x, fb(g->n_cols, F)), in(h, fb(E, F)), {dy, nullptr, fb(g->n_rows, F)},
+                   out(dx, fb(g->n_cols, F)), out(dh, fb(E, F)), out(dscores, fb(E, H)), {nullptr, nullptr, dscores ? fb(E, H) : 0}},
+                  [&](std::vector<void *> &p) {
+                      const float *a = (float *)p[0], *d = (float *)p[3];
+                      if (dx)
+                          if (int rc = athena_mp_attn_gather_bwd_x(g, F, H, a, d, (float *)p[4])) return rc;
+                      if (dh)
+                          if (int rc = athena_mp_attn_gather_bwd_edges(g, F, H, a, d, (float *)p[5])) return rc;
+                      if (!dscores) return 0;
+                      if (int rc = athena_mp_attn_gather_bwd_alpha(g, F, H, x ? (float *)p[1] : nullptr, h ? (float *)p[2] : nullptr, d,
+                                                                   (float *)p[7]))
+                          return rc;
+                      return athena_mp_attn_softmax_bwd(g, H, a, (float *)p[7], (float *)p[6]);
+                  });
+}
 // ---- the edge MLP's input (edge_gather.hip): h goes up as well as down, so that its pad columns keep the caller's words ------------
 int athena_mp_edge_gather_host(const athena_mp_graph *g, int32_t Fs, const float *xs, int32_t Fq, const float *xq, int32_t dim,
                                const float *coords, int32_t relative, int32_t ld, float *h)

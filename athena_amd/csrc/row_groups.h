@@ -1,4 +1,4 @@
-// Lane groups over the rows of a CSR: the kernel scheme of interp.hip, pool.hip and edge_gather.hip, held once.
+// Lane groups over the rows of a CSR: the kernel scheme of interp.hip, pool.hip, edge_gather.hip and attention.hip, held once.
 //
 // G lanes share a row, G the smallest power of two from 4 with 4 G >= F (a full wave from F = 193; more columns than 256 take
 // further passes), so no lane idles at F = 16, 64, 128, 256.  The group's lanes load what they need of G entries, one entry per

@@ -63,6 +63,9 @@ module athena_mp_c
   public :: athena_mp_interp_host, athena_mp_interp_bwd_host
   public :: athena_mp_pool_max_fwd, athena_mp_pool_max_edges_fwd, athena_mp_pool_max_bwd_x, athena_mp_pool_max_bwd_edges
   public :: athena_mp_pool_max_host, athena_mp_pool_max_bwd_host
+  public :: athena_mp_attn_softmax_fwd, athena_mp_attn_gather_fwd, athena_mp_attn_gather_edges_fwd, athena_mp_attn_gather_bwd_x
+  public :: athena_mp_attn_gather_bwd_edges, athena_mp_attn_gather_bwd_alpha, athena_mp_attn_softmax_bwd
+  public :: athena_mp_attention_host, athena_mp_attention_bwd_host
   public :: athena_mp_edge_gather_fwd, athena_mp_edge_gather_bwd, athena_mp_edge_gather_host, athena_mp_edge_gather_bwd_host
   public :: athena_mp_periodic_pairs, athena_mp_periodic_graph_host, athena_mp_periodic_stats
   public :: athena_mp_edge_grad_to_points, athena_mp_periodic_grad
@@ -927,6 +930,72 @@ module athena_mp_c
        integer(c_int32_t), value :: F
        integer(c_int32_t), intent(in) :: arg(F, *)
        real(c_float), intent(in) :: dy(F, *)
+     end function
+     !! attention pooling over a handle's rows (definition: include/athena_mp.h), on a handle with one entry per edge column; H = n_heads,
+     !! the head of feature c (0-based) is c / (F / H).  The softmax over each row's entries, per head: scores (H, E) -> alpha (H, E)
+     integer(c_int) function athena_mp_attn_softmax_fwd(graph, n_heads, scores_dev, alpha_dev) bind(C, name="athena_mp_attn_softmax_fwd")
+       import :: c_int, c_int32_t, c_ptr
+       type(c_ptr), value :: graph, scores_dev, alpha_dev
+       integer(c_int32_t), value :: n_heads
+     end function
+     !! the weighted sum over each row, the weight chosen per head: alpha (H, E), x (F, n_cols) -> y (F, n_rows)
+     integer(c_int) function athena_mp_attn_gather_fwd(graph, F, n_heads, alpha_dev, x_dev, y_dev) bind(C, name="athena_mp_attn_gather_fwd")
+       import :: c_int, c_int32_t, c_ptr
+       type(c_ptr), value :: graph, alpha_dev, x_dev, y_dev
+       integer(c_int32_t), value :: F, n_heads
+     end function
+     !! ... the same over per-edge values h (F, E)
+     integer(c_int) function athena_mp_attn_gather_edges_fwd(graph, F, n_heads, alpha_dev, h_dev, y_dev) &
+          bind(C, name="athena_mp_attn_gather_edges_fwd")
+       import :: c_int, c_int32_t, c_ptr
+       type(c_ptr), value :: graph, alpha_dev, h_dev, y_dev
+       integer(c_int32_t), value :: F, n_heads
+     end function
+     !! the reverse of the vertex form: dy (F, n_rows) -> dx (F, n_cols), each column's sum over its queries, ascending
+     integer(c_int) function athena_mp_attn_gather_bwd_x(graph, F, n_heads, alpha_dev, dy_dev, dx_dev) &
+          bind(C, name="athena_mp_attn_gather_bwd_x")
+       import :: c_int, c_int32_t, c_ptr
+       type(c_ptr), value :: graph, alpha_dev, dy_dev, dx_dev
+       integer(c_int32_t), value :: F, n_heads
+     end function
+     !! the reverse of the edge form: dy (F, n_rows) -> dh (F, E) = alpha * dy of the edge's row
+     integer(c_int) function athena_mp_attn_gather_bwd_edges(graph, F, n_heads, alpha_dev, dy_dev, dh_dev) &
+          bind(C, name="athena_mp_attn_gather_bwd_edges")
+       import :: c_int, c_int32_t, c_ptr
+       type(c_ptr), value :: graph, alpha_dev, dy_dev, dh_dev
+       integer(c_int32_t), value :: F, n_heads
+     end function
+     !! the reverse with respect to the weights: exactly one of x_dev (F, n_cols) and h_dev (F, E), the other c_null_ptr -> dalpha (H, E)
+     integer(c_int) function athena_mp_attn_gather_bwd_alpha(graph, F, n_heads, x_dev, h_dev, dy_dev, dalpha_dev) &
+          bind(C, name="athena_mp_attn_gather_bwd_alpha")
+       import :: c_int, c_int32_t, c_ptr
+       type(c_ptr), value :: graph, x_dev, h_dev, dy_dev, dalpha_dev
+       integer(c_int32_t), value :: F, n_heads
+     end function
+     !! the reverse of the softmax: alpha, dalpha (H, E) -> dscores (H, E)
+     integer(c_int) function athena_mp_attn_softmax_bwd(graph, n_heads, alpha_dev, dalpha_dev, dscores_dev) &
+          bind(C, name="athena_mp_attn_softmax_bwd")
+       import :: c_int, c_int32_t, c_ptr
+       type(c_ptr), value :: graph, alpha_dev, dalpha_dev, dscores_dev
+       integer(c_int32_t), value :: n_heads
+     end function
+     !! the same with host arrays (staged): scores (H, E) -> alpha (c_loc of (H, E), or c_null_ptr) and y (F, n_rows) over exactly one of
+     !! x (F, n_cols) and h (F, E): c_loc of the host array, the other c_null_ptr
+     integer(c_int) function athena_mp_attention_host(graph, F, n_heads, scores, x, h, alpha, y) bind(C, name="athena_mp_attention_host")
+       import :: c_int, c_int32_t, c_float, c_ptr
+       type(c_ptr), value :: graph, x, h, alpha
+       integer(c_int32_t), value :: F, n_heads
+       real(c_float), intent(in) :: scores(n_heads, *)
+       real(c_float), intent(inout) :: y(F, *)
+     end function
+     !! ... and alpha (H, E), the same one of x and h, dy (F, n_rows) -> dx (F, n_cols) or dh (F, E), and dscores (H, E): c_loc of the
+     !! host arrays, or c_null_ptr (not all three)
+     integer(c_int) function athena_mp_attention_bwd_host(graph, F, n_heads, alpha, x, h, dy, dx, dh, dscores) &
+          bind(C, name="athena_mp_attention_bwd_host")
+       import :: c_int, c_int32_t, c_float, c_ptr
+       type(c_ptr), value :: graph, x, h, dx, dh, dscores
+       integer(c_int32_t), value :: F, n_heads
+       real(c_float), intent(in) :: alpha(n_heads, *), dy(F, *)
      end function
      !! the edge MLP's input over a two-set handle (definition: include/athena_mp.h): h (ld, E), column e = xs(:, j) (relative = 1:
      !! less xq(:, i)), then xq(:, i), then coords(:, e) for the entry (i, j) of edge e; ld >= Fs + Fq + dim, the elements beyond

@@ -51,6 +51,16 @@ the maximum over each sample's neighbourhood, with the arg-max that the reverse 
 pool_max(handle, x=...) takes per-vertex values instead (on any handle, square ones too) and pool_max_grad(..., to="x") is its
 reverse.  edge_features(..., x_queries=..., relative=True) makes EdgeConv's input (x_j - x_i, x_i).
 
+The third reduction over the same neighbourhoods is attention (athena_amd/csrc/attention.hip): a softmax over each row's entries, per
+head, and the weighted sum with the weight chosen per head -- edge_features -> MLP -> attention_weights -> attend:
+
+    m = edge_features(handle, x_sources=x, x_queries=x_coarse, coords=coords, relative=True, pad_to=4)
+    ... the edge MLPs on m return scores [E, H] and values h [E, F], F a multiple of H (H = F: vector attention)
+    alpha = attention_weights(handle, scores)                           # [E, H]: each row's entries add up to 1, per head
+    y = attend(handle, alpha, edges=h)                                  # [n_coarse, F]; or attend(handle, alpha, x=x) over vertex values
+    ... the layers above return dy [n_coarse, F]
+    g = attend_grad(handle, alpha, dy, edges=h)                         # g["values"] [E, F] (dh; dx [n_points, F] with x=), g["scores"] [E, H]
+
 For LARGE clouds the coarse set comes from a voxel grid instead (athena_amd/csrc/grid_clusters.hip): O(n), no dependent steps, one
 coarse point -- the centroid -- per non-empty cubic cell, and the membership as the pooling handle:
 
@@ -274,6 +284,99 @@ def pool_max_grad(handle, arg, dy, to="x", out=None):
     _capi.call("athena_mp_pool_max_bwd_x" if to == "x" else "athena_mp_pool_max_bwd_edges", handle.handle, F, C.c_void_p(arg.data_ptr()),
                C.c_void_p(dy.data_ptr()), C.c_void_p(out.data_ptr()))
     return out
+
+
+def _heads(F, H):
+    if H < 1 or F < 1 or F % H != 0:
+        raise ValueError(f"F = {F} feature columns do not divide into H = {H} heads")
+
+
+def attention_weights(handle, scores, out=None):
+    """The softmax over each row's entries, per head (athena_mp_attn_softmax_fwd; the definition is in include/athena_mp.h): scores
+    [E, H], a contiguous float32 device tensor, one row per edge of a handle with one entry per edge column (from_point_sets,
+    from_point_sets_knn).  Returns alpha [E, H]: over the entries of row i in CSR order, alpha = exp(s - max) / sum; each non-empty
+    (row, head) adds up to 1 but for rounding, a -inf score gives exactly 0, a NaN or +inf (or only -inf) makes its own (row, head)
+    NaN and no other.  out: a contiguous float32 device tensor [E, H] to write into."""
+    import torch
+
+    scores = _device_f32(scores, (handle.n_edge_cols, None), "scores")
+    E, H = handle.n_edge_cols, int(scores.shape[1])
+    _heads(H, H)
+    if out is None:
+        out = torch.empty((E, H), dtype=torch.float32, device=scores.device)
+    out = _device_f32(out, (E, H), "out")
+    _capi.use_torch_stream()
+    _capi.call("athena_mp_attn_softmax_fwd", handle.handle, H, C.c_void_p(scores.data_ptr()), C.c_void_p(out.data_ptr()))
+    return out
+
+
+def _attend_values(handle, x, edges):
+    """(values, "x" or "edges"): exactly one of the two is given"""
+    if (x is None) == (edges is None):
+        raise ValueError("exactly one of x and edges must be given")
+    if x is not None:
+        return _device_f32(x, (handle.n_cols, None), "x"), "x"
+    return _device_f32(edges, (handle.n_edge_cols, None), "edges"), "edges"
+
+
+def attend(handle, alpha, x=None, edges=None, out=None):
+    """y [n_rows, F] = the sum over each row of the handle of alpha times the values, the weight chosen per head
+    (athena_mp_attn_gather_fwd, athena_mp_attn_gather_edges_fwd): alpha [E, H] as attention_weights returned it -- or any weights of
+    that shape --, and exactly one of x [n_cols, F] (per-vertex values) and edges [E, F] (per-edge values), F a multiple of H;
+    feature column c takes the weight of head c // (F // H).  Bit for bit the sequential fp32 sum in CSR order; an empty row gives
+    0.  H = 1 is interpolate; H = F is vector attention.  out: a contiguous float32 device tensor [n_rows, F] to write into."""
+    import torch
+
+    v, form = _attend_values(handle, x, edges)
+    alpha = _device_f32(alpha, (handle.n_edge_cols, None), "alpha")
+    F, H = int(v.shape[1]), int(alpha.shape[1])
+    _heads(F, H)
+    if out is None:
+        out = torch.empty((handle.n_rows, F), dtype=torch.float32, device=v.device)
+    out = _device_f32(out, (handle.n_rows, F), "out")
+    _capi.use_torch_stream()
+    _capi.call("athena_mp_attn_gather_fwd" if form == "x" else "athena_mp_attn_gather_edges_fwd", handle.handle, F, H,
+               C.c_void_p(alpha.data_ptr()), C.c_void_p(v.data_ptr()), C.c_void_p(out.data_ptr()))
+    return out
+
+
+def attend_grad(handle, alpha, dy, x=None, edges=None, want=("values", "scores"), out=None):
+    """The reverse of attend, and of attention_weights under it: alpha [E, H] as the forward used it, dy [n_rows, F], and the one of
+    x and edges that the forward took.  Returns a dict of device tensors for the names in `want`: "values", the gradient with
+    respect to the values -- dx [n_cols, F], row j = the sum over the handle's column j, queries ascending, of alpha * dy[i]
+    (athena_mp_attn_gather_bwd_x), or dh [E, F] = alpha * dy[i] (athena_mp_attn_gather_bwd_edges), both bit-defined --; "scores"
+    [E, H], the gradient with respect to the scores of attention_weights, through athena_mp_attn_gather_bwd_alpha (the sum over
+    each head's columns of dy * values) and athena_mp_attn_softmax_bwd.  out: a dict of contiguous float32 device tensors to write
+    into, by the same names."""
+    import torch
+
+    want = tuple(want)
+    if not want or any(w not in ("values", "scores") for w in want):
+        raise ValueError('want must name some of ("values", "scores")')
+    v, form = _attend_values(handle, x, edges)
+    E = handle.n_edge_cols
+    alpha = _device_f32(alpha, (E, None), "alpha")
+    F, H = int(v.shape[1]), int(alpha.shape[1])
+    _heads(F, H)
+    dy = _device_f32(dy, (handle.n_rows, F), "dy")
+    shapes = {"values": (handle.n_cols if form == "x" else E, F), "scores": (E, H)}
+    res = {}
+    for w in want:
+        t = None if out is None else out.get(w)
+        if t is None:
+            t = torch.empty(shapes[w], dtype=torch.float32, device=dy.device)
+        res[w] = _device_f32(t, shapes[w], f"out[{w!r}]")
+    ptr = lambda t: C.c_void_p(t.data_ptr())
+    _capi.use_torch_stream()
+    if "values" in want:
+        _capi.call("athena_mp_attn_gather_bwd_x" if form == "x" else "athena_mp_attn_gather_bwd_edges", handle.handle, F, H, ptr(alpha),
+                   ptr(dy), ptr(res["values"]))
+    if "scores" in want:
+        dalpha = torch.empty((E, H), dtype=torch.float32, device=dy.device)
+        _capi.call("athena_mp_attn_gather_bwd_alpha", handle.handle, F, H, ptr(v) if form == "x" else None,
+                   ptr(v) if form == "edges" else None, ptr(dy), ptr(dalpha))
+        _capi.call("athena_mp_attn_softmax_bwd", handle.handle, H, ptr(alpha), ptr(dalpha), ptr(res["scores"]))
+    return res
 
 
 def _device_rows(t, rows, cols, what):

@@ -563,6 +563,60 @@ int athena_mp_pool_max_bwd_edges(const athena_mp_graph *g, int32_t F, const int3
  * reverse of the vertex form, and dh [E, F], the reverse of the edge form, both from the one arg; each may be NULL, not both. */
 int athena_mp_pool_max_host(const athena_mp_graph *g, int32_t F, const float *x, const float *h, float *y, int32_t *arg);
 int athena_mp_pool_max_bwd_host(const athena_mp_graph *g, int32_t F, const int32_t *arg, const float *dy, float *dx, float *dh);
+/* Attention pooling over a handle's rows (attention.hip): a softmax over each row's entries, per head, then the weighted sum of
+ * per-vertex or per-edge values with the weight chosen per head, and every reverse step -- the reduction of Point Transformer's
+ * vector attention, of GAT-style set abstraction and of the attention kernels of transformer neural operators over a mesh and a
+ * latent set.  Nothing in the reference corresponds to them.
+ * Definition.  g is a handle with one entry per edge column (what the edge forms of interp and pool accept).  Row i is the forward
+ * CSR (rowptr, col, eid), column j the transposed one (t_rowptr, t_src, t_eid; queries ascending).  H >= 1 heads, F >= 1,
+ * F % H == 0, C = F / H; the head of feature column c is c / C.  Everything is fp32, every operation rounded on its own, no
+ * contraction.  Arrays are row-major; E is the number of edge columns.
+ *   athena_mp_attn_softmax_fwd  scores [E, H] -> alpha [E, H].  For row i and head h, over the entries k in CSR order, e = eid[k]:
+ *     m = the maximum of scores[e, h];  p_k = exp(scores[e, h] - m);  S = p_0 + p_1 + ... in CSR order;  alpha[e, h] = p_k / S.
+ *     So a -inf beside a finite maximum gives alpha exactly +0; a (row, head) whose scores hold a NaN or a +inf, or only -inf, is
+ *     NaN in all of its entries and no other (row, head) is touched; a row of one finite entry gives exactly 1; an empty row
+ *     writes nothing.  exp is the expf of athena_mp_softmax_fwd; alpha is held to that entry's bound, not to bits.
+ *   athena_mp_attn_gather_fwd        alpha, x [n_cols, F] -> y [n_rows, F]:  acc = +0; for k = rowptr[i] .. in order:
+ *                                    acc = acc + alpha[eid[k], c / C] * x[col[k], c];  y[i, c] = acc
+ *   athena_mp_attn_gather_edges_fwd  alpha, h [E, F] -> y:  the same with h[eid[k], c] in the place of x[col[k], c]
+ *     Bit for bit the sequential sum; an empty row gives +0.  At H = 1 the vertex form writes the bytes of athena_mp_interp_fwd.
+ *   athena_mp_attn_gather_bwd_x      alpha, dy [n_rows, F] -> dx [n_cols, F]:  acc = +0; for k = t_rowptr[j] .. in order:
+ *                                    acc = acc + alpha[t_eid[k], c / C] * dy[t_src[k], c];  dx[j, c] = acc.  A column without
+ *                                    entries gives +0.
+ *   athena_mp_attn_gather_bwd_edges  alpha, dy -> dh [E, F]:  the entry k of row i, e = eid[k]:  dh[e, c] = alpha[e, c / C] * dy[i, c]
+ *   athena_mp_attn_gather_bwd_alpha  exactly one of x and h (the other NULL), dy -> dalpha [E, H]:  the entry k of row i, e = eid[k]:
+ *                                    dalpha[e, h] = the sum over the C columns c of head h of dy[i, c] * v, v = x[col[k], c] or
+ *                                    h[e, c].  The order of this sum is the implementation's; at C = 1 there is none, and
+ *                                    dalpha is the product itself.
+ *   athena_mp_attn_softmax_bwd       alpha, dalpha -> dscores [E, H]:  dot = +0; for k in CSR order: dot = dot + alpha[e, h] *
+ *                                    dalpha[e, h];  then dscores[e, h] = alpha[e, h] * (dalpha[e, h] - dot).  Bit-defined from the
+ *                                    given alpha and dalpha.
+ *   Every element of every output is written, but for alpha, dalpha, dh and dscores along an empty row, which has no entry.  No
+ *   atomics: two runs are byte-identical.
+ * Refused with a message: what athena_mp_pool_max_edges_fwd refuses of a handle; H < 1; F < 1; F % H != 0; for bwd_alpha both or
+ * neither of x and h.  The library stays usable after a refusal.  Empty sets succeed (empty arrays may be NULL).  A caller's
+ * pointer needs only 4-byte alignment; with F % 4 == 0 (softmax: H % 4 == 0) and every array on a 16-byte boundary the rows move
+ * 16 bytes at a time -- the same bytes, sooner. */
+int athena_mp_attn_softmax_fwd(const athena_mp_graph *g, int32_t H, const float *scores_dev, float *alpha_dev);
+int athena_mp_attn_gather_fwd(const athena_mp_graph *g, int32_t F, int32_t H, const float *alpha_dev, const float *x_dev, float *y_dev);
+int athena_mp_attn_gather_edges_fwd(const athena_mp_graph *g, int32_t F, int32_t H, const float *alpha_dev, const float *h_dev,
+                                    float *y_dev);
+int athena_mp_attn_gather_bwd_x(const athena_mp_graph *g, int32_t F, int32_t H, const float *alpha_dev, const float *dy_dev,
+                                float *dx_dev);
+int athena_mp_attn_gather_bwd_edges(const athena_mp_graph *g, int32_t F, int32_t H, const float *alpha_dev, const float *dy_dev,
+                                    float *dh_dev);
+int athena_mp_attn_gather_bwd_alpha(const athena_mp_graph *g, int32_t F, int32_t H, const float *x_dev, const float *h_dev,
+                                    const float *dy_dev, float *dalpha_dev);
+int athena_mp_attn_softmax_bwd(const athena_mp_graph *g, int32_t H, const float *alpha_dev, const float *dalpha_dev,
+                               float *dscores_dev);
+/* The same for callers that hold Fortran arrays, staged through HBM.  athena_mp_attention_host: scores [E, H] -> alpha [E, H] (may be
+ * NULL) and y [n_rows, F] over exactly one of x [n_cols, F] and h [E, F].  athena_mp_attention_bwd_host: alpha as the forward
+ * returned it, the same one of x and h, dy [n_rows, F] -> dx [n_cols, F] (with x) or dh [E, F] (with h), and dscores [E, H] through
+ * bwd_alpha and softmax_bwd; a NULL output is skipped, not all three. */
+int athena_mp_attention_host(const athena_mp_graph *g, int32_t F, int32_t H, const float *scores, const float *x, const float *h,
+                             float *alpha, float *y);
+int athena_mp_attention_bwd_host(const athena_mp_graph *g, int32_t F, int32_t H, const float *alpha, const float *x, const float *h,
+                                 const float *dy, float *dx, float *dh, float *dscores);
 /* The gather that makes the edge MLP's input over a two-set handle, with its reverse (edge_gather.hip): h[e, :] = (xs[col], xq[row],
  * coords[e]) for every entry, the step between athena_mp_knn_pairs_bipartite and the MLP of PointNet++'s set abstraction and of
  * EdgeConv (relative: the first block is xs[col] - xq[row]), whose output athena_mp_pool_max_edges_fwd reduces; and back from the
