@@ -93,6 +93,14 @@ _PROTOS = {
     "athena_mp_attn_softmax_bwd": [_vp, _i32, _vp, _vp, _vp],
     "athena_mp_attention_host": [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp],
     "athena_mp_attention_bwd_host": [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "athena_mp_triplet_pairs": [_vp, _i32, _vp, _f32, _vp, _i64, _vp, C.POINTER(_i64)],
+    "athena_mp_entry_vectors_fwd": [_vp, _i32, _vp, _vp],
+    "athena_mp_entry_vectors_bwd": [_vp, _i32, _vp, _vp],
+    "athena_mp_triplet_cos_fwd": [_vp, _i32, _vp, _vp],
+    "athena_mp_triplet_cos_bwd": [_vp, _i32, _vp, _vp, _vp, _vp],
+    "athena_mp_triplet_stats": [_vp],
+    "athena_mp_triplets_host": [_vp, _i32, _vp, _f32, _vp, _vp, _i64, _vp, _vp, C.POINTER(_i64)],
+    "athena_mp_triplet_cos_bwd_host": [_vp, _i32, _vp, _f32, _i64, _vp, _vp],
     "athena_mp_edge_gather_fwd": [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _vp],
     "athena_mp_edge_gather_bwd": [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp],
     "athena_mp_edge_gather_host": [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _vp],

@@ -66,6 +66,8 @@ module athena_mp_c
   public :: athena_mp_attn_softmax_fwd, athena_mp_attn_gather_fwd, athena_mp_attn_gather_edges_fwd, athena_mp_attn_gather_bwd_x
   public :: athena_mp_attn_gather_bwd_edges, athena_mp_attn_gather_bwd_alpha, athena_mp_attn_softmax_bwd
   public :: athena_mp_attention_host, athena_mp_attention_bwd_host
+  public :: athena_mp_triplet_pairs, athena_mp_entry_vectors_fwd, athena_mp_entry_vectors_bwd, athena_mp_triplet_cos_fwd
+  public :: athena_mp_triplet_cos_bwd, athena_mp_triplet_stats, athena_mp_triplets_host, athena_mp_triplet_cos_bwd_host
   public :: athena_mp_edge_gather_fwd, athena_mp_edge_gather_bwd, athena_mp_edge_gather_host, athena_mp_edge_gather_bwd_host
   public :: athena_mp_periodic_pairs, athena_mp_periodic_graph_host, athena_mp_periodic_stats
   public :: athena_mp_edge_grad_to_points, athena_mp_periodic_grad
@@ -930,6 +932,68 @@ module athena_mp_c
        integer(c_int32_t), value :: F
        integer(c_int32_t), intent(in) :: arg(F, *)
        real(c_float), intent(in) :: dy(F, *)
+     end function
+     !! bond-angle triplets of a square handle with edge columns (definition: include/athena_mp.h): pairs_dev (2, capacity) int32, the
+     !! 1-based entry pairs athena_mp_graph_create_bipartite_dev(nnz, nnz, T, ...) takes; rowptr_dev (nnz + 1) int32 or c_null_ptr; both
+     !! c_null_ptr: size query.  vec_dev (dim, E) may be c_null_ptr with cutoff3 = +infinity
+     integer(c_int) function athena_mp_triplet_pairs(graph, dim, vec_dev, cutoff3, pairs_dev, capacity, rowptr_dev, n_triplets) &
+          bind(C, name="athena_mp_triplet_pairs")
+       import :: c_int, c_int32_t, c_int64_t, c_float, c_ptr
+       type(c_ptr), value :: graph, vec_dev, pairs_dev, rowptr_dev
+       integer(c_int32_t), value :: dim
+       real(c_float), value :: cutoff3
+       integer(c_int64_t), value :: capacity
+       integer(c_int64_t), intent(out) :: n_triplets
+     end function
+     !! vec (dim, E) -> dir (dim, nnz), the vector from each entry's row vertex to its neighbour, and back: ddir -> dvec
+     integer(c_int) function athena_mp_entry_vectors_fwd(graph, dim, vec_dev, dir_dev) bind(C, name="athena_mp_entry_vectors_fwd")
+       import :: c_int, c_int32_t, c_ptr
+       type(c_ptr), value :: graph, vec_dev, dir_dev
+       integer(c_int32_t), value :: dim
+     end function
+     integer(c_int) function athena_mp_entry_vectors_bwd(graph, dim, ddir_dev, dvec_dev) bind(C, name="athena_mp_entry_vectors_bwd")
+       import :: c_int, c_int32_t, c_ptr
+       type(c_ptr), value :: graph, ddir_dev, dvec_dev
+       integer(c_int32_t), value :: dim
+     end function
+     !! on the triplet handle: dir (dim, nnz) -> cos (T), and dir, cos, dcos (T) -> ddir (dim, nnz)
+     integer(c_int) function athena_mp_triplet_cos_fwd(tgraph, dim, dir_dev, cos_dev) bind(C, name="athena_mp_triplet_cos_fwd")
+       import :: c_int, c_int32_t, c_ptr
+       type(c_ptr), value :: tgraph, dir_dev, cos_dev
+       integer(c_int32_t), value :: dim
+     end function
+     integer(c_int) function athena_mp_triplet_cos_bwd(tgraph, dim, dir_dev, cos_dev, dcos_dev, ddir_dev) &
+          bind(C, name="athena_mp_triplet_cos_bwd")
+       import :: c_int, c_int32_t, c_ptr
+       type(c_ptr), value :: tgraph, dir_dev, cos_dev, dcos_dev, ddir_dev
+       integer(c_int32_t), value :: dim
+     end function
+     !! triplets, participants and the longest run of the last athena_mp_triplet_pairs
+     integer(c_int) function athena_mp_triplet_stats(stats) bind(C, name="athena_mp_triplet_stats")
+       import :: c_int, c_int64_t
+       integer(c_int64_t), intent(out) :: stats(3)
+     end function
+     !! the same with host arrays: adj_ia (nnz + 1) 1-based, adj_ja (2, capacity) (second entry, triplet id), c_null_ptr for the size
+     !! query; dir (dim, nnz) and cos (T): c_loc of the host arrays, or c_null_ptr; vec: c_loc of (dim, E), or c_null_ptr
+     integer(c_int) function athena_mp_triplets_host(graph, dim, vec, cutoff3, adj_ia, adj_ja, capacity, dir, cosv, n_triplets) &
+          bind(C, name="athena_mp_triplets_host")
+       import :: c_int, c_int32_t, c_int64_t, c_float, c_ptr
+       type(c_ptr), value :: graph, vec, adj_ia, adj_ja, dir, cosv
+       integer(c_int32_t), value :: dim
+       real(c_float), value :: cutoff3
+       integer(c_int64_t), value :: capacity
+       integer(c_int64_t), intent(out) :: n_triplets
+     end function
+     !! ... and dcos (n_triplets) -> dvec (dim, E) in one call; the triplet handle is built and freed inside
+     integer(c_int) function athena_mp_triplet_cos_bwd_host(graph, dim, vec, cutoff3, n_triplets, dcos, dvec) &
+          bind(C, name="athena_mp_triplet_cos_bwd_host")
+       import :: c_int, c_int32_t, c_int64_t, c_float, c_ptr
+       type(c_ptr), value :: graph
+       integer(c_int32_t), value :: dim
+       real(c_float), value :: cutoff3
+       integer(c_int64_t), value :: n_triplets
+       real(c_float), intent(in) :: vec(dim, *), dcos(*)
+       real(c_float), intent(inout) :: dvec(dim, *)
      end function
      !! attention pooling over a handle's rows (definition: include/athena_mp.h), on a handle with one entry per edge column; H = n_heads,
      !! the head of feature c (0-based) is c / (F / H).  The softmax over each row's entries, per head: scores (H, E) -> alpha (H, E)

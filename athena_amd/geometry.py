@@ -71,7 +71,18 @@ coarse point -- the centroid -- per non-empty cubic cell, and the membership as 
     up, coords, eoff = DeviceGraph.from_point_sets_knn(points, centroid, k=3, query_offsets=offsets, source_offsets=cluster_offsets)
     w, wsum = interp_weights(up, coords);  z = interpolate(up, w, y_coarse)             # the way up, [n_points, F]
     ... the reverse pass returns dcentroid [n_clusters, dim]
-    dpoints = grid_clusters_grad(cluster, handle, dcentroid)            # [n_points, dim]"""
+    dpoints = grid_clusters_grad(cluster, handle, dcentroid)            # [n_points, dim]
+
+Three-body terms (athena_amd/csrc/triplets.hip): the pairs of bonds that meet at an atom and the angle between them, as a handle over
+the CSR entries of the neighbour graph, so that the row kernels above run on it over per-bond messages and per-triplet values:
+
+    handle, feature, vec, voff, eoff = DeviceGraph.from_structures(frac, lat, offsets, cutoff_min, cutoff_max)
+    thandle, dir = DeviceGraph.from_triplets(handle, vec, cutoff=cutoff3)   # rows = columns = CSR entries, one edge per triplet
+    cos = triplet_cos(thandle, dir)                                     # [T]
+    ... edge_features(thandle, x_sources=m, ...) -> MLP -> attend / interpolate / pool_max on thandle ... return dcos [T]
+    ddir = triplet_cos_grad(thandle, dir, cos, dcos)                    # [nnz, 3]
+    dvec = entry_vectors_grad(handle, ddir)                             # [E, 3]
+    g = structures_grad(handle, lat, voff, eoff, vec, cutoff_max, dvec=dvec)"""
 import ctypes as C
 
 import numpy as np
@@ -647,3 +658,86 @@ def structures_grad_host(handle, lat, offsets, edge_offsets, vec, cutoff_max, df
     _capi.call("athena_mp_periodic_grad_host", handle.handle, B, n, vp(off), vp(eoff), vp(lat), float(cutoff_max), vp(vec), vp(dfeature),
                fe_cols, vp(dvec), vp(res.get("cart")), vp(res.get("frac")), vp(res.get("virial")), vp(res.get("lat")))
     return res
+
+
+def entry_vectors(handle, vec, out=None):
+    """The vector from every entry's row vertex to its neighbour (athena_mp_entry_vectors_fwd; the definition is in
+    include/athena_mp.h): handle is a square handle with edge columns (from_structures, from_points, from_point_clouds[_knn],
+    from_edges) and vec [E, dim] what its builder returned (smaller index minus larger), a contiguous float32 device tensor, dim
+    1..3.  Returns dir [nnz, dim], one row per CSR entry k of row i and column c: -vec[e] when i <= c, +vec[e] when i > c, +0 for an
+    id-less self loop.  DeviceGraph.from_triplets returns the same tensor; the chain is from_structures -> from_triplets ->
+    triplet_cos -> ... -> triplet_cos_grad -> entry_vectors_grad -> structures_grad(dvec=...).  out: a contiguous float32 device
+    tensor [nnz, dim] to write into."""
+    import torch
+
+    vec = _device_f32(vec, (handle.n_edge_cols, None), "vec")
+    dim = int(vec.shape[1])
+    if out is None:
+        out = torch.empty((handle.nnz, dim), dtype=torch.float32, device=vec.device)
+    out = _device_f32(out, (handle.nnz, dim), "out")
+    _capi.use_torch_stream()
+    _capi.call("athena_mp_entry_vectors_fwd", handle.handle, dim, C.c_void_p(vec.data_ptr()), C.c_void_p(out.data_ptr()))
+    return out
+
+
+def entry_vectors_grad(handle, ddir, out=None):
+    """The reverse of entry_vectors (athena_mp_entry_vectors_bwd): ddir [nnz, dim] float32 on the device -> dvec [E, dim], row e the
+    signed sum of ddir over the entries that carry edge e, in the order of the handle's edge index (- where the entry's row is at
+    most its column, + where it is larger); bit for bit the sequential sum.  dvec is what structures_grad takes as dvec=, and
+    points_grad as dcoords.  out: a contiguous float32 device tensor [E, dim] to write into."""
+    import torch
+
+    ddir = _device_f32(ddir, (handle.nnz, None), "ddir")
+    dim = int(ddir.shape[1])
+    if out is None:
+        out = torch.empty((handle.n_edge_cols, dim), dtype=torch.float32, device=ddir.device)
+    out = _device_f32(out, (handle.n_edge_cols, dim), "out")
+    _capi.use_torch_stream()
+    _capi.call("athena_mp_entry_vectors_bwd", handle.handle, dim, C.c_void_p(ddir.data_ptr()), C.c_void_p(out.data_ptr()))
+    return out
+
+
+def triplet_cos(thandle, dir, out=None):
+    """The cosine of the angle of every triplet (athena_mp_triplet_cos_fwd; the definition, term by term in fp32, is in
+    include/athena_mp.h): thandle and dir [nnz, dim] as DeviceGraph.from_triplets returned them.  Returns cos [T] float32 on the
+    device: for triplet t = (k, k'), dot(dir[k], dir[k']) / (|dir[k]| |dir[k']|), +0 where the denominator is 0 (coincident points);
+    no clamp, so |cos| may exceed 1 by rounding.  cos is a per-edge value of thandle: interpolate(thandle, cos, m),
+    pool_max(thandle, edges=cos[:, None]), edge_features and attend take it as it is.  out: a contiguous float32 device tensor [T]
+    to write into."""
+    import torch
+
+    dir = _device_f32(dir, (thandle.n_rows, None), "dir")
+    T = thandle.n_edge_cols
+    if out is None:
+        out = torch.empty((T,), dtype=torch.float32, device=dir.device)
+    out = _device_f32(out, (T,), "out")
+    _capi.use_torch_stream()
+    _capi.call("athena_mp_triplet_cos_fwd", thandle.handle, int(dir.shape[1]), C.c_void_p(dir.data_ptr()), C.c_void_p(out.data_ptr()))
+    return out
+
+
+def triplet_cos_grad(thandle, dir, cos, dcos, out=None):
+    """The reverse of triplet_cos (athena_mp_triplet_cos_bwd): dir [nnz, dim] and cos [T] as the forward took and returned them, dcos
+    [T] float32 on the device -> ddir [nnz, dim]: row k sums dcos[t] times the gradient of cos[t] with respect to dir[k], first over
+    the triplets whose first entry is k (row k of thandle in CSR order), then over those whose second entry is k (its column, rows
+    ascending); bit for bit the sequential sum, +0 for an entry in no triplet.  entry_vectors_grad carries ddir on to dvec, and
+    structures_grad(dvec=...) to atoms and cell.  out: a contiguous float32 device tensor [nnz, dim] to write into."""
+    import torch
+
+    dir = _device_f32(dir, (thandle.n_rows, None), "dir")
+    dim, T = int(dir.shape[1]), thandle.n_edge_cols
+    cos, dcos = _device_f32(cos, (T,), "cos"), _device_f32(dcos, (T,), "dcos")
+    if out is None:
+        out = torch.empty((thandle.n_rows, dim), dtype=torch.float32, device=dir.device)
+    out = _device_f32(out, (thandle.n_rows, dim), "out")
+    ptr = lambda t: C.c_void_p(t.data_ptr())
+    _capi.use_torch_stream()
+    _capi.call("athena_mp_triplet_cos_bwd", thandle.handle, dim, ptr(dir), ptr(cos), ptr(dcos), ptr(out))
+    return out
+
+
+def triplet_stats():
+    """(triplets, participants, the longest run m (m - 1)) of the last triplet build (athena_mp_triplet_stats)"""
+    out = np.zeros(3, np.int64)
+    _capi.call("athena_mp_triplet_stats", out.ctypes.data_as(C.c_void_p))
+    return tuple(int(v) for v in out)

@@ -864,6 +864,54 @@ class DeviceGraph:
         return self, feature, vec, off.copy(), eoff
 
     @classmethod
+    def from_triplets(cls, handle, vec=None, cutoff=None, device=0):
+        """A square handle with edge columns -> the handle over its bond-angle triplets, without the pair list leaving HBM
+        (athena_mp_triplet_pairs, then athena_mp_graph_create_bipartite_dev): every ordered pair (k, k') of distinct CSR entries of
+        one vertex row is a triplet, numbered in lexicographic order; the definition is in include/athena_mp.h.  handle: from
+        from_structures, from_points, from_point_clouds[_knn] or from_edges (with edge ids); vec [E, dim] float32 as its builder
+        returned it, a numpy array or a torch tensor already on the device; cutoff: the shorter three-body cutoff -- only entries
+        with |vec| < cutoff take part (None: every entry with an edge id; vec may then be None too).  One size query, then one
+        fill.  Returns (thandle, dir), or (thandle, None) without vec: thandle.n_rows = thandle.n_cols = handle.nnz, one CSR entry
+        and one edge column per triplet (thandle.n_edge_cols = T), so per-entry messages are its vertex values and per-triplet
+        values its edge values; dir [nnz, dim] is geometry.entry_vectors(handle, vec), what geometry.triplet_cos takes."""
+        import torch
+
+        _capi.init(device)
+        dev = torch.device("cuda", device)
+        if vec is not None:
+            if isinstance(vec, torch.Tensor):
+                vec = vec.to(dev, torch.float32).contiguous()
+            else:
+                vec = torch.from_numpy(np.ascontiguousarray(vec, dtype=np.float32)).to(dev)
+            if vec.dim() != 2 or int(vec.shape[0]) != handle.n_edge_cols:
+                raise ValueError(f"vec must be [{handle.n_edge_cols}, dim]")
+        elif cutoff is not None:
+            raise ValueError("a cutoff needs vec")
+        dim = int(vec.shape[1]) if vec is not None else 3
+        cutoff3 = float("inf") if cutoff is None else float(cutoff)
+        _capi.use_torch_stream()
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        T = C.c_int64()
+        _capi.call("athena_mp_triplet_pairs", handle.handle, dim, ptr(vec), cutoff3, None, 0, None, C.byref(T))
+        pairs = torch.empty((T.value, 2), dtype=torch.int32, device=dev)       # the memory of a column-major [2, T]
+        _capi.call("athena_mp_triplet_pairs", handle.handle, dim, ptr(vec), cutoff3, ptr(pairs), T.value, None, C.byref(T))
+        self = cls.__new__(cls)
+        nnz = handle.nnz
+        ia = np.empty(nnz + 1, np.int32)
+        h = C.c_void_p()
+        _capi.call("athena_mp_graph_create_bipartite_dev", nnz, nnz, T.value, ptr(pairs), ia.ctypes.data_as(C.c_void_p), None, 0,
+                   C.byref(h))
+        self.handle = h
+        self.n_rows = self.n_cols = nnz
+        self.nnz = int(T.value)
+        self.n_edge_cols = int(T.value)
+        if vec is None:
+            return self, None
+        from . import geometry
+
+        return self, geometry.entry_vectors(handle, vec)
+
+    @classmethod
     def borrow(cls, handle, owner=None):
         """wrap a handle somebody else owns (the row blocks of an athena_mp_shard): never destroyed from here"""
         self = cls.__new__(cls)

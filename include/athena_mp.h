@@ -665,6 +665,65 @@ int athena_mp_edge_gather_host(const athena_mp_graph *g, int32_t Fs, const float
                                const float *coords, int32_t relative, int32_t ld, float *h);
 int athena_mp_edge_gather_bwd_host(const athena_mp_graph *g, int32_t Fs, int32_t Fq, int32_t dim, int32_t relative, int32_t ld,
                                    const float *dh, float *dxs, float *dxq, float *dcoords);
+/* Bond-angle triplets of a neighbour graph on the device, with gradients (triplets.hip): for every vertex the ordered pairs of bonds
+ * that meet there and the cosine of the angle between them -- the three-body terms of DimeNet, M3GNet and ALIGNN -- and the way back
+ * from a gradient per triplet to the builders' vec, which athena_mp_periodic_grad takes as dvec.  The triplets are a graph over the
+ * CSR ENTRIES of a handle (its line graph): athena_mp_graph_create_bipartite_dev(nnz, nnz, T, pairs, ...) makes a handle of the pair
+ * list, and the row kernels (athena_mp_edge_gather_fwd, athena_mp_interp_fwd, athena_mp_pool_max_edges_fwd, athena_mp_attn_*) run on
+ * it over per-entry messages and per-triplet values.  Nothing in the reference corresponds to them.
+ * Definition.  All integer results are exact.  All arithmetic is fp32, every operation rounded on its own, / and sqrt correctly
+ * rounded.  g is a square handle with edge columns (built with_edge_ids = 1, add_self_loops or not).  Entry k is a 0-based position of
+ * its forward CSR as athena_mp_graph_export shows it; i is its row, c = col[k], e = eid[k].
+ *   Entry vectors (athena_mp_entry_vectors_fwd), vec [E, dim] -> dir [nnz, dim], the vector from vertex i to the neighbour of entry k:
+ *     dir[k] = -vec[e] when i <= c;  dir[k] = +vec[e] when i > c;  dir[k] = +0 when e < 0 (an id-less self loop).
+ *     vec has the builders' sign (smaller index minus larger).  A periodic self-image edge (c == i) is one entry per image; +shift and
+ *     -shift are separate edges, so -vec[e] is right for both.
+ *   Their reverse (athena_mp_entry_vectors_bwd), ddir [nnz, dim] -> dvec [E, dim]:  dvec[e] = acc, acc = +0, then over the entries of
+ *     edge column e in the order of the handle's edge index (athena_mp_graph_export 8, 10): acc = acc - ddir[k] when i <= c, acc = acc
+ *     + ddir[k] when i > c.  Every element of dvec is written.
+ *   Participants (athena_mp_triplet_pairs).  cutoff3 = +infinity: every entry with e >= 0; vec may then be NULL.  Otherwise an entry
+ *     takes part iff e >= 0 and r < cutoff3, with s = ((x0 * x0) + x1 * x1) + x2 * x2 over x = vec[e] and r = sqrt(s) -- the builder's
+ *     own s and r, the comparison strict: the separate, shorter three-body cutoff of M3GNet.
+ *   Triplets.  Every ordered pair (k, k') of distinct participants of one vertex row is a triplet; two images of the same neighbour
+ *     (same col, different eid) are distinct entries.  Triplets are numbered in lexicographic order of (k, k').  pairs [2, capacity]
+ *     int32, column-major, 1-based, is exactly the list athena_mp_graph_create_bipartite_dev(nnz, nnz, T, pairs, ...) takes: strictly
+ *     ascending, one edge id per triplet.  rowptr [nnz + 1] int32, 0-based (may be NULL): rowptr[k] = the triplets whose first entry
+ *     lies before k, rowptr[nnz] = T.  A row with m participants gives m (m - 1) triplets in one contiguous run.  Two builds of the
+ *     same input are byte-identical.
+ *   Angle (athena_mp_triplet_cos_fwd), on the triplet handle tg, dir -> cos [T].  For triplet t = (k, k'), a = dir[k], b = dir[k'],
+ *     over the first dim components, dim in 1..3:
+ *       sa = ((a0 * a0) + a1 * a1) + a2 * a2, sb likewise;  dot = ((a0 * b0) + a1 * b1) + a2 * b2;  den = sqrt(sa) * sqrt(sb);
+ *       cos[t] = dot / den.  Where den == 0 (coincident points of a radius graph; never in a periodic graph), cos[t] = +0 and both
+ *     gradient terms below are +0.  There is no clamp: |cos| may exceed 1 by rounding.
+ *   Its reverse (athena_mp_triplet_cos_bwd), dir, cos, dcos [T] -> ddir [nnz, dim]:
+ *       ga_c = b_c / den - (cos[t] * a_c) / sa;  gb_c = a_c / den - (cos[t] * b_c) / sb.
+ *     ddir[k] = acc, acc = +0.  First over the triplets of row k of tg in CSR order: acc = acc + dcos[t] * ga.  Then over the entries of
+ *     column k in the order of its transposed CSR (rows ascending): acc = acc + dcos[t] * gb.  An entry in no triplet gives +0; every
+ *     element of ddir is written.  No atomics anywhere.
+ * athena_mp_triplet_pairs with pairs_dev and rowptr_dev both NULL is a size query (the count pass only).  Refused with a message: a
+ * handle without edge columns; a handle that is not square; dim outside 1..3; cutoff3 NaN or <= 0; vec NULL with a finite cutoff3; T
+ * >= 2^31 (found by the count pass in 64-bit arithmetic, before anything of that size is allocated; the count is named); capacity < T.
+ * nnz = 0 or T = 0 succeeds.  The cos entries are refused unless tg is square and carries one edge id per entry (what
+ * athena_mp_pool_max_edges_fwd asks of a handle).  The library stays usable after a refusal.  Pointers need 4-byte alignment only.
+ * athena_mp_triplet_stats: out = {triplets, participants, the longest run m (m - 1)} of the last athena_mp_triplet_pairs. */
+int athena_mp_triplet_pairs(const athena_mp_graph *g, int32_t dim, const float *vec_dev, float cutoff3, int32_t *pairs_dev,
+                            int64_t capacity, int32_t *rowptr_dev, int64_t *n_triplets_out);
+int athena_mp_entry_vectors_fwd(const athena_mp_graph *g, int32_t dim, const float *vec_dev, float *dir_dev);
+int athena_mp_entry_vectors_bwd(const athena_mp_graph *g, int32_t dim, const float *ddir_dev, float *dvec_dev);
+int athena_mp_triplet_cos_fwd(const athena_mp_graph *tg, int32_t dim, const float *dir_dev, float *cos_dev);
+int athena_mp_triplet_cos_bwd(const athena_mp_graph *tg, int32_t dim, const float *dir_dev, const float *cos_dev, const float *dcos_dev,
+                              float *ddir_dev);
+int athena_mp_triplet_stats(int64_t out[3]);
+/* The same for callers that hold Fortran arrays.  athena_mp_triplets_host: the triplet CSR in the conventions of
+ * athena_mp_radius_graph_bipartite_host -- adj_ia [nnz + 1] (1-based), adj_ja [2, capacity] column-major (second entry k', triplet id:
+ * one directed entry per triplet) -- and, each may be NULL, dir [nnz, dim] and cos [T]; vec [E, dim] may be NULL with cutoff3 =
+ * +infinity when neither is asked for.  adj_ja_out == NULL: size query for *n_triplets_out.  athena_mp_triplet_cos_bwd_host: dcos
+ * [n_triplets] -> dvec [E, dim] in one call (entry vectors, cos, both reverse steps); it builds and frees the triplet handle inside,
+ * and refuses an n_triplets that is not the graph's count. */
+int athena_mp_triplets_host(const athena_mp_graph *g, int32_t dim, const float *vec, float cutoff3, int32_t *adj_ia_out,
+                            int32_t *adj_ja_out, int64_t capacity, float *dir_out, float *cos_out, int64_t *n_triplets_out);
+int athena_mp_triplet_cos_bwd_host(const athena_mp_graph *g, int32_t dim, const float *vec, float cutoff3, int64_t n_triplets,
+                                   const float *dcos, float *dvec_out);
 /* athena_mp_edge_grad_to_points and athena_mp_periodic_grad with every array on the host (a handle plus Fortran arrays), staged
  * through HBM */
 int athena_mp_edge_grad_to_points_host(const athena_mp_graph *g, int32_t dim, const float *dcoords, float *dpoints);
