@@ -62,6 +62,13 @@ _PROTOS = {
     "athena_mp_grid_clusters_host": [_i32, _i32, _vp, _i32, _vp, _f32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "athena_mp_grid_clusters_grad_host": [_i32, _i32, _i32, _vp, _vp, _vp, _vp],
     "athena_mp_grid_clusters_stats": [_vp],
+    "athena_mp_contract_pairs": [_i64, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp,
+                                 _vp, _vp],
+    "athena_mp_contract_pairs_host": [_i64, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp,
+                                      _vp, _vp, _vp],
+    "athena_mp_contract_stats": [_vp],
+    "athena_mp_graph_pairs": [_vp, _vp, _i64],
+    "athena_mp_cell_pairs": [_i32, _i64, _i32, _vp, _vp, _i64, _vp],
     "athena_mp_periodic_pairs": [_i32, _i32, _vp, _vp, _vp, _vp, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp],
     "athena_mp_periodic_graph_host": [_i32, _i32, _vp, _vp, _vp, _vp, _f32, _f32, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp,
                                       _vp],

@@ -59,6 +59,8 @@ module athena_mp_c
   public :: athena_mp_farthest_points, athena_mp_farthest_points_host, athena_mp_fps_stats
   public :: athena_mp_grid_clusters, athena_mp_grid_clusters_grad, athena_mp_grid_clusters_host, athena_mp_grid_clusters_grad_host
   public :: athena_mp_grid_clusters_stats
+  public :: athena_mp_contract_pairs, athena_mp_contract_pairs_host, athena_mp_contract_stats, athena_mp_graph_pairs
+  public :: athena_mp_cell_pairs
   public :: athena_mp_interp_weights, athena_mp_interp_fwd, athena_mp_interp_bwd_x, athena_mp_interp_bwd_coords
   public :: athena_mp_interp_host, athena_mp_interp_bwd_host
   public :: athena_mp_pool_max_fwd, athena_mp_pool_max_edges_fwd, athena_mp_pool_max_bwd_x, athena_mp_pool_max_bwd_edges
@@ -757,6 +759,57 @@ module athena_mp_c
      integer(c_int) function athena_mp_grid_clusters_stats(out) bind(C, name="athena_mp_grid_clusters_stats")
        import :: c_int, c_int64_t
        integer(c_int64_t), intent(out) :: out(4)
+     end function
+     !! a pair list relabelled through a vertex map and merged (definition: include/athena_mp.h): graph contraction over a cluster
+     !! map, the induced subgraph of a selection (id 0 drops a vertex), the merge of duplicate pairs (no maps).  Everything on the
+     !! device: pairs (2, n_pairs), row_cluster (n_rows), col_cluster (n_cols) (c_null_ptr: the identity), row_points
+     !! (dim, m_rows), col_points (dim, m_cols) (both or neither); outputs coarse_pairs (2, capacity), rowptr (capacity + 1,
+     !! 0-based), members (2, member_capacity) = (coarse pair, fine edge), weights (member_capacity), edge_pair (n_pairs), coords
+     !! (dim, capacity), each may be c_null_ptr (all six: the counts only).  mode 0: undirected, one set; 1: directed, two sets
+     integer(c_int) function athena_mp_contract_pairs(n_pairs, pairs_dev, n_rows, n_cols, row_cluster_dev, col_cluster_dev, m_rows, &
+          m_cols, mode, dim, row_points_dev, col_points_dev, capacity, member_capacity, coarse_pairs_dev, rowptr_dev, members_dev, &
+          weights_dev, edge_pair_dev, coords_dev, n_coarse, n_members) bind(C, name="athena_mp_contract_pairs")
+       import :: c_int, c_int32_t, c_int64_t, c_ptr
+       integer(c_int64_t), value :: n_pairs, capacity, member_capacity
+       integer(c_int32_t), value :: n_rows, n_cols, m_rows, m_cols, mode, dim
+       type(c_ptr), value :: pairs_dev, row_cluster_dev, col_cluster_dev, row_points_dev, col_points_dev
+       type(c_ptr), value :: coarse_pairs_dev, rowptr_dev, members_dev, weights_dev, edge_pair_dev, coords_dev
+       integer(c_int64_t), intent(out) :: n_coarse, n_members
+     end function
+     !! the same with host arrays, staged through HBM: pairs (2, n_pairs); the maps, the points and the six outputs as c_loc of
+     !! host arrays of the shapes above, or c_null_ptr
+     integer(c_int) function athena_mp_contract_pairs_host(n_pairs, pairs, n_rows, n_cols, row_cluster, col_cluster, m_rows, m_cols, &
+          mode, dim, row_points, col_points, capacity, member_capacity, coarse_pairs, rowptr, members, weights, edge_pair, coords, &
+          n_coarse, n_members) bind(C, name="athena_mp_contract_pairs_host")
+       import :: c_int, c_int32_t, c_int64_t, c_ptr
+       integer(c_int64_t), value :: n_pairs, capacity, member_capacity
+       integer(c_int32_t), intent(in) :: pairs(2, *)
+       integer(c_int32_t), value :: n_rows, n_cols, m_rows, m_cols, mode, dim
+       type(c_ptr), value :: row_cluster, col_cluster, row_points, col_points
+       type(c_ptr), value :: coarse_pairs, rowptr, members, weights, edge_pair, coords
+       integer(c_int64_t), intent(out) :: n_coarse, n_members
+     end function
+     !! the last contraction call: coarse pairs, members, key bits sorted, members of the largest coarse pair
+     integer(c_int) function athena_mp_contract_stats(out) bind(C, name="athena_mp_contract_stats")
+       import :: c_int, c_int64_t
+       integer(c_int64_t), intent(out) :: out(4)
+     end function
+     !! a handle's pair list on the device: pairs (2, n_edge_cols), (row, column) of the first entry that carries each edge column
+     integer(c_int) function athena_mp_graph_pairs(graph, pairs_dev, capacity) bind(C, name="athena_mp_graph_pairs")
+       import :: c_int, c_int64_t, c_ptr
+       type(c_ptr), value :: graph, pairs_dev
+       integer(c_int64_t), value :: capacity
+     end function
+     !! mesh elements -> pair list on the device: cells (nv, n_cells) 1-based; cell_type 1 segment, 2 triangle, 3 quadrilateral
+     !! (its ring), 4 tetrahedron; pairs (2, capacity), slot (c - 1) * ne + l = local pair l of cell c; pairs_dev = c_null_ptr: the
+     !! count and the check only
+     integer(c_int) function athena_mp_cell_pairs(n_vertices, n_cells, cell_type, cells_dev, pairs_dev, capacity, n_pairs) &
+          bind(C, name="athena_mp_cell_pairs")
+       import :: c_int, c_int32_t, c_int64_t, c_ptr
+       integer(c_int32_t), value :: n_vertices, cell_type
+       integer(c_int64_t), value :: n_cells, capacity
+       type(c_ptr), value :: cells_dev, pairs_dev
+       integer(c_int64_t), intent(out) :: n_pairs
      end function
      !! periodic structures -> pair list and edge geometry on the device, a batch per call (replaces get_graph_from_basis;
      !! definition: include/athena_mp.h).  offsets (n_structures + 1) and pbc (3) on the host; frac (3, n_atoms) and

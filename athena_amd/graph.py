@@ -755,6 +755,176 @@ class DeviceGraph:
             out += (cells[:m, :dim].clone(),)
         return out
 
+    def pair_list(self):
+        """The handle's pair list written on the device (athena_mp_graph_pairs): an int32 tensor [n_edge_cols, 2], the memory of a
+        column-major [2, n_edge_cols], 1-based; edge column e holds (row, column) of the first CSR entry that carries it -- (min,
+        max) of input pair e on a from_edges handle, the pair itself on a rectangular one -- and (0, 0) where no entry does."""
+        import torch
+
+        _capi.use_torch_stream()
+        E = int(self.n_edge_cols)
+        pairs = torch.empty((E, 2), dtype=torch.int32, device=torch.device("cuda", torch.cuda.current_device()))
+        _capi.call("athena_mp_graph_pairs", self.handle, C.c_void_p(pairs.data_ptr()), E)
+        return pairs
+
+    @classmethod
+    def from_contraction(cls, graph, cluster, n_clusters, col_cluster=None, n_col_clusters=None, points=None, col_points=None,
+                         add_self_loops=False, want_pool=True, n_vertices=None, n_col_vertices=None, device=0):
+        """A graph contracted over a cluster map -> the coarse device handle that keeps the fine graph's adjacency, and the handle
+        that pools per-edge features, without a list leaving HBM (athena_mp_graph_pairs, athena_mp_contract_pairs, then
+        athena_mp_graph_create_from_edges_dev or athena_mp_graph_create_bipartite_dev): every fine pair is relabelled through the
+        map, the distinct results are the coarse pairs in lexicographic order, their fine edges the members in edge-id order; the
+        definition is in include/athena_mp.h.  graph: a DeviceGraph with edge columns, or a device int32 tensor [E, 2] (the memory
+        of a column-major [2, E], 1-based, 0 = no such edge) together with n_vertices= (and n_col_vertices= for a two-set list).
+        cluster [n_rows] int32 on the device or numpy, values 0 .. n_clusters, 0 drops the vertex: what from_grid_clusters
+        returns, as it is; None: the identity (n_clusters must be n_rows), which merges duplicate pairs.  The mode follows the
+        graph: square and no col_cluster is undirected (self pairs of clusters go, pairs are (min, max)); n_cols != n_rows or a
+        col_cluster given (with n_col_clusters) is directed, two sets.  points [n_clusters, dim] (and col_points
+        [n_col_clusters, dim] in the directed mode) float32, dim 1..3: the coarse positions, e.g. the centroids.  One size query
+        and one call.  Returns (coarse_handle, coarse_pairs, pool_handle, weights, edge_pair) and, with points, coords last:
+        coarse_pairs int32 [P, 2] on the device; pool_handle (None without want_pool) has n_rows = P coarse pairs, n_cols = E fine
+        edges, one entry per member: pool_max(pool_handle, x=h) is max pooling of fine edge features h [E, F],
+        interpolate(pool_handle, weights, h) mean pooling; weights float32 [M]; edge_pair int32 [E], the coarse pair of each fine
+        edge, 0 where it takes no part (unpooling is h_coarse[edge_pair - 1]); coords float32 [P, dim] = points[a] - points[b],
+        the coarse handle's GNO edge input."""
+        import torch
+
+        if isinstance(graph, DeviceGraph):
+            if n_vertices is not None or n_col_vertices is not None:
+                raise ValueError("n_vertices belongs to a pair list; a DeviceGraph knows its own")
+            if graph.n_edge_cols <= 0:
+                raise ValueError("the handle has no edge columns: there is no pair list to contract")
+            n_rows, n_cols = int(graph.n_rows), int(graph.n_cols)
+            pairs = None
+        else:
+            if not (isinstance(graph, torch.Tensor) and graph.dtype == torch.int32 and graph.dim() == 2 and graph.shape[1] == 2):
+                raise ValueError("graph must be a DeviceGraph or a device int32 tensor [E, 2]")
+            if n_vertices is None:
+                raise ValueError("a pair list needs n_vertices")
+            n_rows = int(n_vertices)
+            n_cols = n_rows if n_col_vertices is None else int(n_col_vertices)
+            pairs = graph
+        mode = 1 if (n_cols != n_rows or col_cluster is not None) else 0
+        if mode == 1 and cluster is not None and col_cluster is None:
+            raise ValueError("a two-set graph needs col_cluster beside cluster")
+        if mode == 1 and points is not None and col_points is None:
+            raise ValueError("a two-set graph needs col_points beside points")
+        if mode == 0 and (col_points is not None or n_col_clusters is not None):
+            raise ValueError("col_points and n_col_clusters belong to the two-set mode: give col_cluster")
+        m_rows = int(n_clusters)
+        m_cols = m_rows if mode == 0 else int(n_col_clusters if n_col_clusters is not None else (n_cols if col_cluster is None else -1))
+        if m_cols < 0:
+            raise ValueError("col_cluster needs n_col_clusters")
+        for a, what, rows in ((cluster, "cluster", n_rows), (col_cluster, "col_cluster", n_cols), (points, "points", m_rows),
+                              (col_points, "col_points", m_cols)):
+            if a is not None and int(a.shape[0]) != rows:
+                raise ValueError(f"{what} must have {rows} rows, not {int(a.shape[0])}")
+        _capi.init(device)
+        dev = torch.device("cuda", device)
+        if pairs is not None:
+            pairs = pairs.to(dev).contiguous()
+
+        def on_device(a, dt, what, rows):
+            if a is None:
+                return None
+            if isinstance(a, torch.Tensor):
+                return a.to(dev, dt).contiguous()
+            return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32 if dt == torch.int32 else np.float32)).to(dev)
+
+        rc = on_device(cluster, torch.int32, "cluster", n_rows)
+        cc = rc if mode == 0 else on_device(col_cluster, torch.int32, "col_cluster", n_cols)
+        rp = on_device(points, torch.float32, "points", m_rows)
+        cp = rp if mode == 0 else on_device(col_points, torch.float32, "col_points", m_cols)
+        dim = 0
+        if rp is not None:
+            if rp.dim() != 2 or cp.dim() != 2 or rp.shape[1] != cp.shape[1]:
+                raise ValueError("points must be [n_clusters, dim], the same dim on both sides")
+            dim = int(rp.shape[1])
+        _capi.use_torch_stream()
+        if pairs is None:
+            pairs = graph.pair_list()
+        E = int(pairs.shape[0])
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        vp = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+        P, M = C.c_int64(), C.c_int64()
+        head = (E, ptr(pairs), n_rows, n_cols, ptr(rc), ptr(cc), m_rows, m_cols, mode, dim, ptr(rp), ptr(cp))
+        _capi.call("athena_mp_contract_pairs", *head, 0, 0, None, None, None, None, None, None, C.byref(P), C.byref(M))
+        P, M = int(P.value), int(M.value)
+        coarse_pairs = torch.empty((P, 2), dtype=torch.int32, device=dev)      # the memory of a column-major [2, P]
+        members = torch.empty((M, 2), dtype=torch.int32, device=dev) if want_pool else None
+        weights = torch.empty((M,), dtype=torch.float32, device=dev)
+        edge_pair = torch.empty((E,), dtype=torch.int32, device=dev)
+        coords = torch.empty((P, dim), dtype=torch.float32, device=dev) if rp is not None else None
+        P2, M2 = C.c_int64(), C.c_int64()
+        _capi.call("athena_mp_contract_pairs", *head, P, M, ptr(coarse_pairs), None, ptr(members), ptr(weights), ptr(edge_pair), ptr(coords),
+                   C.byref(P2), C.byref(M2))
+        self = cls.__new__(cls)
+        h = C.c_void_p()
+        ia = np.empty(m_rows + 1, np.int32)
+        if mode == 0:
+            nnz = C.c_int64()
+            _capi.call("athena_mp_graph_create_from_edges_dev", m_rows, P, ptr(coarse_pairs), int(bool(add_self_loops)), 1, vp(ia), None, 0,
+                       C.byref(nnz), C.byref(h))
+            self.nnz = int(nnz.value)
+        else:
+            _capi.call("athena_mp_graph_create_bipartite_dev", m_rows, m_cols, P, ptr(coarse_pairs), vp(ia), None, 0, C.byref(h))
+            self.nnz = P
+        self.handle = h
+        self.n_rows, self.n_cols = m_rows, m_cols
+        self.n_edge_cols = P
+        pool = None
+        if want_pool:
+            pool = cls.__new__(cls)
+            hp = C.c_void_p()
+            pia = np.empty(P + 1, np.int32)
+            _capi.call("athena_mp_graph_create_bipartite_dev", P, E, M, ptr(members), vp(pia), None, 0, C.byref(hp))
+            pool.handle = hp
+            pool.n_rows, pool.n_cols = P, E
+            pool.nnz = M
+            pool.n_edge_cols = M
+        out = (self, coarse_pairs, pool, weights, edge_pair)
+        if coords is not None:
+            out += (coords,)
+        return out
+
+    _CELLS = {1: (2, 1), 2: (3, 3), 3: (4, 4), 4: (4, 6), "segment": 1, "triangle": 2, "quadrilateral": 3, "tetrahedron": 4}
+
+    @classmethod
+    def from_mesh(cls, cells, n_vertices, cell_type, points=None, add_self_loops=False, want_pool=True, device=0):
+        """Mesh elements -> the device handle of the mesh's edge graph, without a list leaving HBM (athena_mp_cell_pairs, then
+        from_contraction with the identity map): a graph neural operator dataset that arrives as elements.  cells [n_cells, nv]
+        int32, 1-based: a numpy array, or a torch tensor already on the device; cell_type 1 / "segment" (nv = 2), 2 / "triangle"
+        (3), 3 / "quadrilateral" (4, its ring) or 4 / "tetrahedron" (4, all six pairs); points [n_vertices, dim] float32, dim
+        1..3.  Returns what from_contraction returns -- (handle, edges, pool_handle, weights, edge_pair) and, with points, coords
+        last --: edges int32 [P, 2] are the mesh's distinct edges (a < b) in lexicographic order; pool_handle maps the n_cells * ne
+        element-edge slots (slot c * ne + l = local pair l of cell c) onto them, so 1 / weights counts the elements on an edge (1
+        on the boundary of a triangle mesh); edge_pair [n_cells * ne] is the edge of each slot, 0 for the pair of a repeated
+        vertex; coords [P, dim] = points[a] - points[b]."""
+        import torch
+
+        ct = cls._CELLS.get(cell_type, cell_type) if isinstance(cell_type, str) else cell_type
+        if ct not in (1, 2, 3, 4):
+            raise ValueError("cell_type must be 1..4 or one of segment, triangle, quadrilateral, tetrahedron")
+        nv, ne = cls._CELLS[ct]
+        if len(cells.shape) != 2 or cells.shape[1] != nv:
+            raise ValueError(f"cells must be [n_cells, {nv}] for cell_type {ct}")
+        if points is not None and int(points.shape[0]) != int(n_vertices):
+            raise ValueError(f"points must have {int(n_vertices)} rows, not {int(points.shape[0])}")
+        _capi.init(device)
+        dev = torch.device("cuda", device)
+        if isinstance(cells, torch.Tensor):
+            cd = cells.to(dev, torch.int32).contiguous()
+        else:
+            cd = torch.from_numpy(np.ascontiguousarray(cells, dtype=np.int32)).to(dev)
+        n_cells = int(cd.shape[0])
+        _capi.use_torch_stream()
+        pairs = torch.empty((n_cells * ne, 2), dtype=torch.int32, device=dev)  # the memory of a column-major [2, n_cells * ne]
+        count = C.c_int64()
+        _capi.call("athena_mp_cell_pairs", int(n_vertices), n_cells, ct, C.c_void_p(cd.data_ptr()), C.c_void_p(pairs.data_ptr()),
+                   n_cells * ne, C.byref(count))
+        return cls.from_contraction(pairs, None, int(n_vertices), points=points, add_self_loops=add_self_loops, want_pool=want_pool,
+                                    n_vertices=int(n_vertices), device=device)
+
     @classmethod
     def from_point_clouds_knn(cls, points, offsets, k, radius=None, mode="union", add_self_loops=False, want_adjacency=False,
                               want_neighbours=False, device=0):

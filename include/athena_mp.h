@@ -392,6 +392,73 @@ int athena_mp_grid_clusters_grad_host(int32_t n, int32_t dim, int32_t n_clusters
 /* What the last athena_mp_grid_clusters call did: out[0] = clusters, out[1] = the key bits sorted (cloud bits + cell bits), out[2] =
  * the 8-bit passes of the radix sort, out[3] = the members of the largest cluster (0 after a size query). */
 int athena_mp_grid_clusters_stats(int64_t out[4]);
+/* A pair list relabelled through a vertex map and merged, on the device (contract.hip): the contraction of a graph over a cluster
+ * map -- the pooled graph of a graph U-Net or multi-scale MeshGraphNet level, which keeps the fine graph's adjacency instead of a
+ * new geometric search over the centroids --, the induced subgraph of a vertex selection (id 0 drops a vertex), the merge of a
+ * multigraph's duplicate pairs (no maps) and, behind athena_mp_cell_pairs, the edge graph of a mesh.  Every implementation gives
+ * the same arrays.
+ *   Inputs, on the device: pairs [2, n_pairs] int32, column-major, 1-based -- the index_list every builder writes, column = fine
+ *   edge id; an index of 0 is allowed and means "no such edge".  n_rows, n_cols: the index spaces of its two rows (a one-set list
+ *   passes the same value twice).  row_cluster [n_rows], col_cluster [n_cols] int32, values in 0 .. m_rows / 0 .. m_cols, 0 = the
+ *   vertex is dropped; the two may be the same pointer; NULL = the identity, and then m must equal n.  mode 0: undirected, one
+ *   set; mode 1: directed, two sets.  row_points [m_rows, dim], col_points [m_cols, dim] fp32, dim in 1..3: both or neither, may
+ *   be the same pointer.
+ *   Definition.  For fine edge e = (u, v): a = row_cluster[u], b = col_cluster[v].  The edge takes part iff u >= 1, v >= 1, a >= 1,
+ *   b >= 1 and, in mode 0, a != b.  Its coarse key is (min(a, b), max(a, b)) in mode 0 and (a, b) in mode 1.  The coarse pairs are
+ *   the distinct keys, numbered 1-based in lexicographic order; P is their number.  The members of a coarse pair are its fine
+ *   edges in ascending edge id; M is the number of edges that take part.
+ *   Outputs, on the device, each may be NULL alone:
+ *     coarse_pairs [2, capacity] int32      column-major, 1-based, strictly ascending (mode 0: a < b): what
+ *                                           athena_mp_graph_create_from_edges_dev takes in mode 0 and
+ *                                           athena_mp_graph_create_bipartite_dev in mode 1
+ *     rowptr [capacity + 1] int32           0-based: the members in front of each coarse pair, rowptr[P] = M; P + 1 entries written
+ *     members [2, member_capacity] int32    column-major, 1-based: (coarse pair, fine edge), strictly ascending -- the list
+ *                                           athena_mp_graph_create_bipartite_dev(P, n_pairs, M, ...) turns into the edge-pooling
+ *                                           handle
+ *     weights [member_capacity] fp32        one per member: 1 / fl(count) of its coarse pair (mean pooling through
+ *                                           athena_mp_interp_fwd, as athena_mp_grid_clusters)
+ *     edge_pair [n_pairs] int32             the coarse pair of each fine edge, 0 where it takes no part
+ *     coords [capacity, dim] fp32           row_points[a] - col_points[b] per component in fp32: the builders' convention (smaller
+ *                                           index minus larger in mode 0, query minus source in mode 1)
+ *     *n_coarse_out = P, *n_members_out = M (never NULL)
+ *   Of the arrays with capacity rows, P are written; of those with member_capacity rows, M.  All six NULL: a size query.
+ * Refused with a message: a mode outside 0..1; n_pairs >= 2^31 or a negative size; mode 0 with n_rows != n_cols or m_rows !=
+ * m_cols; a NULL map with m != n; only one of the point arrays, dim outside 1..3 with points, coords without points;
+ * bits_for(m_rows) + bits_for(m_cols) > 62, bits_for(v) = the bits of v, at least 1; a pair index outside 0 .. n (the first such
+ * pair is named, nothing is read through it); a cluster id outside 0 .. m (the first such vertex is named; the row map is looked at
+ * first); capacity < P or member_capacity < M with a matching output given.  n_pairs == 0 succeeds with nothing (rowptr[0] = 0)
+ * before the maps are looked at.  The library stays usable after a refusal.  Two calls on the same input are byte-identical. */
+int athena_mp_contract_pairs(int64_t n_pairs, const int32_t *pairs_dev, int32_t n_rows, int32_t n_cols, const int32_t *row_cluster_dev,
+                             const int32_t *col_cluster_dev, int32_t m_rows, int32_t m_cols, int32_t mode, int32_t dim,
+                             const float *row_points_dev, const float *col_points_dev, int64_t capacity, int64_t member_capacity,
+                             int32_t *coarse_pairs_dev, int32_t *rowptr_dev, int32_t *members_dev, float *weights_dev,
+                             int32_t *edge_pair_dev, float *coords_dev, int64_t *n_coarse_out, int64_t *n_members_out);
+/* athena_mp_contract_pairs with every array on the host, for callers that hold Fortran arrays, staged through HBM; the same
+ * arguments, the same arrays.  All six outputs NULL: the size query. */
+int athena_mp_contract_pairs_host(int64_t n_pairs, const int32_t *pairs, int32_t n_rows, int32_t n_cols, const int32_t *row_cluster,
+                                  const int32_t *col_cluster, int32_t m_rows, int32_t m_cols, int32_t mode, int32_t dim,
+                                  const float *row_points, const float *col_points, int64_t capacity, int64_t member_capacity,
+                                  int32_t *coarse_pairs_out, int32_t *rowptr_out, int32_t *members_out, float *weights_out,
+                                  int32_t *edge_pair_out, float *coords_out, int64_t *n_coarse_out, int64_t *n_members_out);
+/* What the last contraction call did: out[0] = P, out[1] = M, out[2] = the key bits sorted (bits_for(m_rows) + bits_for(m_cols) + 1:
+ * the bit on top marks the edges that take no part), out[3] = the members of the largest coarse pair (0 after a size query). */
+int athena_mp_contract_stats(int64_t out[4]);
+/* A handle's pair list, written on the device: pairs [2, n_edge_cols] int32, column-major, 1-based.  For edge column e the pair is
+ * (row + 1, col + 1) of the entry with the smallest CSR index that carries it (athena_mp_graph_export 8, 9, 10 and 1); an edge
+ * column no entry carries gives (0, 0).  On a handle of athena_mp_graph_create_from_edges_dev that is (min(u, v), max(u, v)) of
+ * input pair e; on a handle of athena_mp_graph_create_bipartite_dev the pair itself.  Launched on the library's stream, not
+ * synchronised.  Refused: capacity < n_edge_cols. */
+int athena_mp_graph_pairs(const athena_mp_graph *g, int32_t *pairs_dev, int64_t capacity);
+/* Mesh elements -> a pair list on the device: cells [n_cells, nv] int32 row-major, 1-based.  cell_type 1: segment, nv = 2, 1 pair;
+ * 2: triangle, nv = 3, 3 pairs; 3: quadrilateral, nv = 4, the ring 01 12 23 30; 4: tetrahedron, nv = 4, all 6 pairs.  Simplices
+ * list their pairs in lexicographic local order.  pairs [2, capacity] int32 column-major: slot c * ne + l holds local pair l of
+ * cell c as given, neither ordered nor deduplicated; *n_pairs_out = n_cells * ne; pairs_dev == NULL: the count and the check
+ * only.  Fed to athena_mp_contract_pairs(mode 0, no maps) this is the mesh's edge graph: the differences of rowptr count the
+ * elements on each edge (1 on the boundary of a triangle mesh), the pooling handle maps element-edge slots to edges, and a cell
+ * with a repeated vertex loses that pair by the a != b rule.  Refused with a message: a cell_type outside 1..4; a negative size;
+ * n_cells * ne >= 2^31; a vertex id outside 1 .. n_vertices (the first such cell is named); capacity < n_cells * ne. */
+int athena_mp_cell_pairs(int32_t n_vertices, int64_t n_cells, int32_t cell_type, const int32_t *cells_dev, int32_t *pairs_dev,
+                         int64_t capacity, int64_t *n_pairs_out);
 /* Periodic structures -> neighbour graphs on the device, a batch per call (periodic_graph.hip).  It replaces get_graph_from_basis
  * of the reference's chemical examples (example/example_library/src/mod_read_chemical_graphs.f90:196-278); the step in front of
  * athena_mp_graph_create_from_edges_dev.
