@@ -69,6 +69,13 @@ _PROTOS = {
     "athena_mp_contract_stats": [_vp],
     "athena_mp_graph_pairs": [_vp, _vp, _i64],
     "athena_mp_cell_pairs": [_i32, _i64, _i32, _vp, _vp, _i64, _vp],
+    "athena_mp_topk_vertices": [_i32, _i32, _vp, _vp, _i32, _vp, _i32, _f32, _vp, _vp, _vp, _vp, _vp],
+    "athena_mp_topk_vertices_host": [_i32, _i32, _vp, _vp, _i32, _vp, _i32, _f32, _vp, _vp, _vp, _vp, _vp],
+    "athena_mp_topk_stats": [_vp],
+    "athena_mp_select_rows_fwd": [_i32, _i32, _i32, _vp, _vp, _vp, _vp],
+    "athena_mp_select_rows_bwd": [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
+    "athena_mp_select_rows_host": [_i32, _i32, _i32, _vp, _vp, _vp, _vp],
+    "athena_mp_select_rows_bwd_host": [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
     "athena_mp_periodic_pairs": [_i32, _i32, _vp, _vp, _vp, _vp, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp],
     "athena_mp_periodic_graph_host": [_i32, _i32, _vp, _vp, _vp, _vp, _f32, _f32, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp,
                                       _vp],

@@ -5,7 +5,7 @@
 set -e
 cd "$(dirname "$0")"
 OUT=../libathena_mp.so
-SRCS="capi.hip graph_build.hip radius_graph.hip bipartite_graph.hip knn_graph.hip knn_bipartite.hip fps.hip grid_clusters.hip contract.hip periodic_graph.hip geometry_grad.hip interp.hip pool.hip attention.hip triplets.hip edge_gather.hip batch_select.hip neighbor_sample.hip agg.hip banded_fused.hip gemm.hip gemm_tiled.hip fused.hip fused_dw.hip elementwise.hip duvenaud.hip bucket_plan.hip duv_mfma.hip readout.hip gno.hip gno64.hip train.hip host.hip comm.hip"
+SRCS="capi.hip graph_build.hip radius_graph.hip bipartite_graph.hip knn_graph.hip knn_bipartite.hip fps.hip grid_clusters.hip contract.hip topk_select.hip periodic_graph.hip geometry_grad.hip interp.hip pool.hip attention.hip triplets.hip edge_gather.hip batch_select.hip neighbor_sample.hip agg.hip banded_fused.hip gemm.hip gemm_tiled.hip fused.hip fused_dw.hip elementwise.hip duvenaud.hip bucket_plan.hip duv_mfma.hip readout.hip gno.hip gno64.hip train.hip host.hip comm.hip"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-function"
 mkdir -p ../../build/obj
 objs=""

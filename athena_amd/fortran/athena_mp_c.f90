@@ -61,6 +61,8 @@ module athena_mp_c
   public :: athena_mp_grid_clusters_stats
   public :: athena_mp_contract_pairs, athena_mp_contract_pairs_host, athena_mp_contract_stats, athena_mp_graph_pairs
   public :: athena_mp_cell_pairs
+  public :: athena_mp_topk_vertices, athena_mp_topk_vertices_host, athena_mp_topk_stats
+  public :: athena_mp_select_rows_fwd, athena_mp_select_rows_bwd, athena_mp_select_rows_host, athena_mp_select_rows_bwd_host
   public :: athena_mp_interp_weights, athena_mp_interp_fwd, athena_mp_interp_bwd_x, athena_mp_interp_bwd_coords
   public :: athena_mp_interp_host, athena_mp_interp_bwd_host
   public :: athena_mp_pool_max_fwd, athena_mp_pool_max_edges_fwd, athena_mp_pool_max_bwd_x, athena_mp_pool_max_bwd_edges
@@ -810,6 +812,66 @@ module athena_mp_c
        integer(c_int64_t), value :: n_cells, capacity
        type(c_ptr), value :: cells_dev, pairs_dev
        integer(c_int64_t), intent(out) :: n_pairs
+     end function
+     !! top-k vertex selection per graph from scores on the device (definition: include/athena_mp.h): offsets (n_graphs + 1) on
+     !! the host, 0-based; score (n) on the device; k_each (n_graphs) on the host or c_null_ptr and then k for every graph ->
+     !! cluster (n), selected (m), order (m) on the device, sel_offsets (n_graphs + 1) on the host (c_null_ptr: not wanted);
+     !! selected and order hold the sum of min(k_g, n_g) elements
+     integer(c_int) function athena_mp_topk_vertices(n_graphs, n, offsets, score_dev, k, k_each, has_min_score, min_score, &
+          cluster_dev, selected_dev, order_dev, sel_offsets, n_selected) bind(C, name="athena_mp_topk_vertices")
+       import :: c_int, c_int32_t, c_int64_t, c_float, c_ptr
+       integer(c_int32_t), value :: n_graphs, n, k, has_min_score
+       integer(c_int32_t), intent(in) :: offsets(*)
+       real(c_float), value :: min_score
+       type(c_ptr), value :: score_dev, k_each, cluster_dev, selected_dev, order_dev, sel_offsets
+       integer(c_int64_t), intent(out) :: n_selected
+     end function
+     !! the same with host arrays
+     integer(c_int) function athena_mp_topk_vertices_host(n_graphs, n, offsets, score, k, k_each, has_min_score, min_score, &
+          cluster, selected, order, sel_offsets, n_selected) bind(C, name="athena_mp_topk_vertices_host")
+       import :: c_int, c_int32_t, c_int64_t, c_float, c_ptr
+       integer(c_int32_t), value :: n_graphs, n, k, has_min_score
+       integer(c_int32_t), intent(in) :: offsets(*)
+       real(c_float), intent(in) :: score(*)
+       real(c_float), value :: min_score
+       type(c_ptr), value :: k_each, cluster, selected, order, sel_offsets
+       integer(c_int64_t), intent(out) :: n_selected
+     end function
+     !! the last selection call: graphs on the wave route, graphs on the sort route, key bits sorted, radix passes
+     integer(c_int) function athena_mp_topk_stats(out) bind(C, name="athena_mp_topk_stats")
+       import :: c_int, c_int64_t
+       integer(c_int64_t), intent(out) :: out(4)
+     end function
+     !! the rows of a selection, gated: x (F, n), gate (n) or c_null_ptr, selected (m) -> y (F, m) = x(:, selected) * gate
+     integer(c_int) function athena_mp_select_rows_fwd(n, m, F, selected_dev, x_dev, gate_dev, y_dev) &
+          bind(C, name="athena_mp_select_rows_fwd")
+       import :: c_int, c_int32_t, c_ptr
+       integer(c_int32_t), value :: n, m, F
+       type(c_ptr), value :: selected_dev, x_dev, gate_dev, y_dev
+     end function
+     !! ... and the reverse: cluster (n), dy (F, m) -> dx (F, n), dgate (n) (either may be c_null_ptr; dgate needs x)
+     integer(c_int) function athena_mp_select_rows_bwd(n, m, F, cluster_dev, dy_dev, x_dev, gate_dev, dx_dev, dgate_dev) &
+          bind(C, name="athena_mp_select_rows_bwd")
+       import :: c_int, c_int32_t, c_ptr
+       integer(c_int32_t), value :: n, m, F
+       type(c_ptr), value :: cluster_dev, dy_dev, x_dev, gate_dev, dx_dev, dgate_dev
+     end function
+     !! the two with host arrays
+     integer(c_int) function athena_mp_select_rows_host(n, m, F, selected, x, gate, y) bind(C, name="athena_mp_select_rows_host")
+       import :: c_int, c_int32_t, c_float, c_ptr
+       integer(c_int32_t), value :: n, m, F
+       integer(c_int32_t), intent(in) :: selected(*)
+       real(c_float), intent(in) :: x(F, *)
+       type(c_ptr), value :: gate
+       real(c_float), intent(out) :: y(F, *)
+     end function
+     integer(c_int) function athena_mp_select_rows_bwd_host(n, m, F, cluster, dy, x, gate, dx, dgate) &
+          bind(C, name="athena_mp_select_rows_bwd_host")
+       import :: c_int, c_int32_t, c_float, c_ptr
+       integer(c_int32_t), value :: n, m, F
+       integer(c_int32_t), intent(in) :: cluster(*)
+       real(c_float), intent(in) :: dy(F, *)
+       type(c_ptr), value :: x, gate, dx, dgate
      end function
      !! periodic structures -> pair list and edge geometry on the device, a batch per call (replaces get_graph_from_basis;
      !! definition: include/athena_mp.h).  offsets (n_structures + 1) and pbc (3) on the host; frac (3, n_atoms) and

@@ -82,7 +82,19 @@ the CSR entries of the neighbour graph, so that the row kernels above run on it 
     ... edge_features(thandle, x_sources=m, ...) -> MLP -> attend / interpolate / pool_max on thandle ... return dcos [T]
     ddir = triplet_cos_grad(thandle, dir, cos, dcos)                    # [nnz, 3]
     dvec = entry_vectors_grad(handle, ddir)                             # [E, 3]
-    g = structures_grad(handle, lat, voff, eoff, vec, cutoff_max, dvec=dvec)"""
+    g = structures_grad(handle, lat, voff, eoff, vec, cutoff_max, dvec=dvec)
+
+Graphs WITHOUT coordinates (citation graphs, bond lists) coarsen by learned scores instead (athena_amd/csrc/topk_select.hip): the k
+best-scored vertices of every graph, the induced subgraph through from_contraction, and the kept rows gated by the score:
+
+    score = ... any layer with one output feature (a Kipf layer for SAGPool, a projection for TopKPooling) ... [n]
+    cluster, selected, sel_offsets = topk_vertices(score, offsets, ratio=0.5)
+    coarse, coarse_pairs, pool, w, edge_pair = DeviceGraph.from_contraction(handle, cluster, len(selected))
+    gate = ops.activation("tanh", score)
+    y = select_rows(selected, x, gate)                                  # [m, F]; sel_offsets are the pooled batch's vertex offsets
+    ... the coarse level works on (coarse, y) and returns z [m, F]; on the way up: unpool(cluster, z) [n, F]
+    g = select_rows_grad(cluster, dy, x=x, gate=gate)                   # g["x"] [n, F], g["gate"] [n]
+    dscore = ops.activation_bwd("tanh", gate, g["gate"])"""
 import ctypes as C
 
 import numpy as np
@@ -741,3 +753,154 @@ def triplet_stats():
     out = np.zeros(3, np.int64)
     _capi.call("athena_mp_triplet_stats", out.ctypes.data_as(C.c_void_p))
     return tuple(int(v) for v in out)
+
+
+def _topk_counts(sizes, k, ratio):
+    """k_g [B] int64 from exactly one of k (an int for every graph, or one per graph) and ratio: min(n_g, ceil(float64(ratio) * n_g))"""
+    B = sizes.size
+    if (k is None) == (ratio is None):
+        raise ValueError("exactly one of k and ratio must be given")
+    if ratio is not None:
+        if isinstance(ratio, bool) or not isinstance(ratio, (int, float, np.integer, np.floating)) or not 0 < float(ratio) <= 1:
+            raise ValueError("ratio must be a number in (0, 1]")
+        return np.minimum(sizes, np.ceil(np.float64(ratio) * sizes.astype(np.float64)).astype(np.int64))
+    kk = np.asarray(k)
+    if kk.dtype.kind not in "iu" or kk.ndim > 1 or (kk.ndim == 1 and kk.shape != (B,)):
+        raise ValueError("k must be a non-negative int, or one per graph")
+    kk = np.broadcast_to(kk.astype(np.int64), (B,))
+    if (kk < 0).any():
+        raise ValueError("k must be a non-negative int, or one per graph")
+    return np.minimum(kk, 2 ** 31 - 1)
+
+
+def topk_vertices(score, offsets=None, k=None, ratio=None, min_score=None, want_order=False, device=0):
+    """The k best-scored vertices of every graph of a batch, on the device (athena_mp_topk_vertices; the definition is in
+    include/athena_mp.h): the selection of TopKPooling, SAGPool and ASAPool.  score [n] float32: a numpy array, or a torch tensor
+    already on the device; offsets [B + 1] 0-based on the host (None: one graph), empty graphs allowed.  Exactly one of k (an int
+    for every graph, or one per graph) and ratio in (0, 1] (k_g = min(n_g, ceil(ratio * n_g)), computed in float64) is given;
+    min_score: a kept vertex also has score >= min_score.  Inside a graph the order is value descending, then index ascending; -0
+    equals +0, every NaN lies below -inf.  Returns (cluster, selected, sel_offsets) and, with want_order, order last: cluster int32
+    [n] = the new 1-based id of a kept vertex, 0 otherwise -- what DeviceGraph.from_contraction(handle, cluster, m) takes for the
+    induced subgraph --, selected int32 [m] = the 1-based vertex of each new id (ascending), order int32 [m] = each graph's kept
+    vertices in score order -- device tensors --, sel_offsets numpy int32 [B + 1], the vertex_offsets of the pooled batch."""
+    import torch
+
+    is_tensor = isinstance(score, torch.Tensor)
+    if is_tensor:
+        if score.dtype != torch.float32 or score.dim() != 1:
+            raise ValueError("score must be float32 [n]")
+        n = int(score.shape[0])
+    else:
+        score = np.asarray(score)
+        if score.dtype != np.float32 or score.ndim != 1:
+            raise ValueError("score must be float32 [n]")
+        n = int(score.shape[0])
+    off = np.array([0, n], np.int32) if offsets is None else np.ascontiguousarray(offsets, dtype=np.int32)
+    if off.ndim != 1 or off.size < 1:
+        raise ValueError("offsets must be [B + 1]")
+    B = off.size - 1
+    sizes = np.diff(off.astype(np.int64))
+    if off[0] != 0 or (sizes < 0).any() or off[-1] != n:
+        raise ValueError(f"offsets must ascend from 0 to n = {n}")
+    kk = _topk_counts(sizes, k, ratio).astype(np.int32)
+    if min_score is not None and (isinstance(min_score, bool) or not isinstance(min_score, (int, float, np.integer, np.floating))):
+        raise ValueError("min_score must be a number or None")
+    room = int(np.minimum(kk.astype(np.int64), sizes).sum())
+    _capi.init(device)
+    dev = torch.device("cuda", device)
+    sc = score.to(dev).contiguous() if is_tensor else torch.from_numpy(np.ascontiguousarray(score)).to(dev)
+    cluster = torch.empty((n,), dtype=torch.int32, device=dev)
+    selected = torch.empty((room,), dtype=torch.int32, device=dev)
+    order = torch.empty((room,), dtype=torch.int32, device=dev) if want_order else None
+    soff = np.zeros(B + 1, np.int32)
+    m = C.c_int64()
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    _capi.use_torch_stream()
+    _capi.call("athena_mp_topk_vertices", B, n, vp(off), ptr(sc), 0, vp(kk), int(min_score is not None),
+               float(min_score) if min_score is not None else 0.0, ptr(cluster), ptr(selected), ptr(order), vp(soff), C.byref(m))
+    out = (cluster, selected[:m.value], soff)
+    return out + (order[:m.value],) if want_order else out
+
+
+def topk_stats():
+    """(graphs on the wave route, graphs on the sort route, key bits sorted, radix passes) of the last selection (athena_mp_topk_stats)"""
+    out = np.zeros(4, np.int64)
+    _capi.call("athena_mp_topk_stats", out.ctypes.data_as(C.c_void_p))
+    return tuple(int(v) for v in out)
+
+
+def _ids_1d(t, what):
+    """t is a contiguous int32 device tensor [*], or ValueError"""
+    import torch
+
+    if not (isinstance(t, torch.Tensor) and t.dim() == 1):
+        raise ValueError(f"{what} must be a contiguous int32 device tensor [*]")
+    return _device_i32(t, (int(t.shape[0]),), what)
+
+
+def select_rows(selected, x, gate=None, out=None):
+    """The rows of a selection, gated (athena_mp_select_rows_fwd): y[r] = x[selected[r] - 1] * gate[selected[r] - 1].  selected [m]
+    int32 (1-based) as topk_vertices returned it, x [n, F] and gate [n] (e.g. ops.activation("tanh", score)) contiguous float32
+    device tensors.  Without a gate the rows are copied bit for bit.  out: a contiguous float32 device tensor [m, F] to write into."""
+    import torch
+
+    selected = _ids_1d(selected, "selected")
+    m = int(selected.shape[0])
+    x = _device_f32(x, (None, None), "x")
+    n, F = int(x.shape[0]), int(x.shape[1])
+    if F < 1:
+        raise ValueError("x must have at least one feature column")
+    if gate is not None:
+        gate = _device_f32(gate, (n,), "gate")
+    if out is None:
+        out = torch.empty((m, F), dtype=torch.float32, device=x.device)
+    out = _device_f32(out, (m, F), "out")
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    _capi.use_torch_stream()
+    _capi.call("athena_mp_select_rows_fwd", n, m, F, ptr(selected), ptr(x), ptr(gate), ptr(out))
+    return out
+
+
+def select_rows_grad(cluster, dy, x=None, gate=None, want=("x", "gate"), out=None):
+    """The reverse of select_rows (athena_mp_select_rows_bwd): cluster [n] int32 as topk_vertices returned it and dy [m, F] float32
+    on the device -> a dict of device tensors for the names in `want`: "x" [n, F], dx[v] = dy[cluster[v] - 1] * gate[v], +0 for a
+    dropped vertex (without a gate: unpool); "gate" [n], dgate[v] = the sum over the columns of dy[cluster[v] - 1] * x[v], +0 for
+    a dropped vertex, which needs x [n, F]; ops.activation_bwd carries it on to the scores.  out: a dict of contiguous float32
+    device tensors to write into, by the same names."""
+    import torch
+
+    want = tuple(want)
+    if not want or any(w not in ("x", "gate") for w in want):
+        raise ValueError('want must name some of ("x", "gate")')
+    cluster = _ids_1d(cluster, "cluster")
+    n = int(cluster.shape[0])
+    dy = _device_f32(dy, (None, None), "dy")
+    m, F = int(dy.shape[0]), int(dy.shape[1])
+    if F < 1:
+        raise ValueError("dy must have at least one feature column")
+    if "gate" in want:
+        if x is None:
+            raise ValueError('want "gate" needs x')
+        x = _device_f32(x, (n, F), "x")
+    if gate is not None:
+        gate = _device_f32(gate, (n,), "gate")
+    shapes = {"x": (n, F), "gate": (n,)}
+    res = {}
+    for w in want:
+        t = None if out is None else out.get(w)
+        if t is None:
+            t = torch.empty(shapes[w], dtype=torch.float32, device=dy.device)
+        res[w] = _device_f32(t, shapes[w], f"out[{w!r}]")
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    _capi.use_torch_stream()
+    _capi.call("athena_mp_select_rows_bwd", n, m, F, ptr(cluster), ptr(dy), ptr(x) if "gate" in want else None, ptr(gate), ptr(res.get("x")),
+               ptr(res.get("gate")))
+    return res
+
+
+def unpool(cluster, y, out=None):
+    """The way up from a selection (athena_mp_select_rows_bwd without a gate): x[v] = y[cluster[v] - 1] for a kept vertex, +0 for
+    a dropped one; cluster [n] int32 and y [m, F] float32 on the device -> [n, F].  unpool(cluster, select_rows(selected, x))
+    is x on the kept rows.  out: a contiguous float32 device tensor [n, F] to write into."""
+    return select_rows_grad(cluster, y, want=("x",), out=None if out is None else {"x": out})["x"]

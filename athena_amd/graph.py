@@ -777,7 +777,10 @@ class DeviceGraph:
         definition is in include/athena_mp.h.  graph: a DeviceGraph with edge columns, or a device int32 tensor [E, 2] (the memory
         of a column-major [2, E], 1-based, 0 = no such edge) together with n_vertices= (and n_col_vertices= for a two-set list).
         cluster [n_rows] int32 on the device or numpy, values 0 .. n_clusters, 0 drops the vertex: what from_grid_clusters
-        returns, as it is; None: the identity (n_clusters must be n_rows), which merges duplicate pairs.  The mode follows the
+        returns, as it is, and what geometry.topk_vertices returns for a selection by scores -- score -> topk_vertices ->
+        from_contraction(handle, cluster, m) is the induced subgraph of the kept vertices, geometry.select_rows(selected, x, gate)
+        their gated features and geometry.unpool(cluster, y) the way back up; None: the identity (n_clusters must be n_rows),
+        which merges duplicate pairs.  The mode follows the
         graph: square and no col_cluster is undirected (self pairs of clusters go, pairs are (min, max)); n_cols != n_rows or a
         col_cluster given (with n_col_clusters) is directed, two sets.  points [n_clusters, dim] (and col_points
         [n_col_clusters, dim] in the directed mode) float32, dim 1..3: the coarse positions, e.g. the centroids.  One size query

@@ -459,6 +459,62 @@ int athena_mp_graph_pairs(const athena_mp_graph *g, int32_t *pairs_dev, int64_t 
  * n_cells * ne >= 2^31; a vertex id outside 1 .. n_vertices (the first such cell is named); capacity < n_cells * ne. */
 int athena_mp_cell_pairs(int32_t n_vertices, int64_t n_cells, int32_t cell_type, const int32_t *cells_dev, int32_t *pairs_dev,
                          int64_t capacity, int64_t *n_pairs_out);
+/* Top-k vertex selection per graph from scores, on the device (topk_select.hip): the coarsening rule of TopKPooling (Graph U-Nets),
+ * SAGPool and ASAPool, for graphs without coordinates.  It produces the vertex map athena_mp_contract_pairs takes for an induced
+ * subgraph (id 0 drops a vertex).  Every implementation gives the same arrays.
+ *   Inputs: n_graphs graphs over n vertices; offsets [n_graphs + 1] int32 on the HOST, 0-based, ascending from 0 to n, empty graphs
+ *   allowed; score [n] fp32 on the device; k_host [n_graphs] on the host, or NULL and then k for every graph; has_min_score 0 / 1
+ *   and min_score.
+ *   Order inside a graph: value descending, then vertex index ascending.  -0 and +0 are equal (the value is score + 0.0f).  Every
+ *   NaN, of either sign and any payload, equals every other NaN and lies below -inf.
+ *   Graph g keeps the first min(k_g, n_g) vertices of that order; with has_min_score a kept vertex also has score >= min_score,
+ *   which is false for a NaN (on either side).  Those that pass are a prefix of the order, so the kept set is one too; a graph may
+ *   keep nothing.
+ *   Outputs, each may be NULL alone:
+ *     cluster [n] int32 on the device        the new 1-based id of a kept vertex, 0 otherwise; the new ids number the kept vertices
+ *                                            in ascending vertex index, so graphs stay contiguous and in the fine order
+ *     selected [m] int32 on the device       the 1-based vertex of new id r + 1
+ *     order [m] int32 on the device          per graph its kept vertices, 1-based, in score order: graph g's run starts at
+ *                                            sel_offsets[g], and every prefix of a run is that graph's top-k'
+ *     sel_offsets [n_graphs + 1] int32 on the HOST, 0-based: the kept vertices in front of each graph
+ *     *n_selected_out = m (never NULL)
+ *   selected and order need room for the sum of min(k_g, n_g) elements, which the caller can compute; exactly m are written.  There
+ *   is no size query.  One host wait per call.
+ * Refused with a message: a negative size; offsets that do not start at 0, are not ascending or do not end at n; a negative k (the
+ * first such graph is named); ATHENA_MP_TOPK_ROUTE (a test switch, read at every call: auto, wave, sort) naming anything else, or
+ * wave with a graph of more than 64 vertices.  n == 0 or n_graphs == 0 succeeds with nothing kept.  The library stays usable after
+ * a refusal.  Two calls on the same input are byte-identical. */
+int athena_mp_topk_vertices(int32_t n_graphs, int32_t n, const int32_t *offsets_host, const float *score_dev, int32_t k,
+                            const int32_t *k_host, int32_t has_min_score, float min_score, int32_t *cluster_dev, int32_t *selected_dev,
+                            int32_t *order_dev, int32_t *sel_offsets_host, int64_t *n_selected_out);
+/* athena_mp_topk_vertices with every array on the host, for callers that hold Fortran arrays, staged through HBM; the same
+ * arguments, the same arrays. */
+int athena_mp_topk_vertices_host(int32_t n_graphs, int32_t n, const int32_t *offsets, const float *score, int32_t k,
+                                 const int32_t *k_each, int32_t has_min_score, float min_score, int32_t *cluster_out,
+                                 int32_t *selected_out, int32_t *order_out, int32_t *sel_offsets_out, int64_t *n_selected_out);
+/* What the last selection call did: out[0] = graphs on the wave route (at most 64 vertices, one wave each; empty graphs count
+ * here), out[1] = graphs on the sort route, out[2] = the key bits sorted (32 + bits_for(n_graphs - 1); 0 without a sort), out[3] =
+ * the 8-bit passes of the radix sort. */
+int athena_mp_topk_stats(int64_t out[4]);
+/* The rows of a selection, gated (topk_select.hip).  x [n, F] fp32 row-major, F >= 1; gate [n] fp32 or NULL -- the caller makes it
+ * with athena_mp_activation_fwd on the scores --; selected [m] and cluster [n] as athena_mp_topk_vertices wrote them.
+ *   fwd:  y[r, :] = fl(x[v, :] * gate[v]), v = selected[r] - 1.  Without a gate a copy that keeps every bit: -0, infinities, NaN
+ *         payloads.
+ *   bwd:  dx[v, :] = fl(dy[c - 1, :] * gate[v]), c = cluster[v]; +0 where c = 0; every element of dx [n, F] is written; without a
+ *         gate this is the un-pooling of dy.  dgate[v] = the sum over the columns of fl(dy[c - 1, col] * x[v, col]), exactly +0
+ *         where c = 0: the one result whose summation order is free (a tree over the row's lanes), held to 1e-5 of the sum of the
+ *         terms' magnitudes.  dx_dev or dgate_dev may be NULL; dgate needs x, dx does not.
+ * Launched on the library's stream; the call waits for the check of the ids.  Refused with a message: a negative size; F < 1; a
+ * selected id outside 1 .. n or a cluster id outside 0 .. m (the first such element is named; nothing is read through it).  The
+ * library stays usable after a refusal.  Two calls on the same input are byte-identical, at any alignment of the arrays. */
+int athena_mp_select_rows_fwd(int32_t n, int32_t m, int32_t F, const int32_t *selected_dev, const float *x_dev, const float *gate_dev,
+                              float *y_dev);
+int athena_mp_select_rows_bwd(int32_t n, int32_t m, int32_t F, const int32_t *cluster_dev, const float *dy_dev, const float *x_dev,
+                              const float *gate_dev, float *dx_dev, float *dgate_dev);
+/* ... with every array on the host, staged through HBM. */
+int athena_mp_select_rows_host(int32_t n, int32_t m, int32_t F, const int32_t *selected, const float *x, const float *gate, float *y);
+int athena_mp_select_rows_bwd_host(int32_t n, int32_t m, int32_t F, const int32_t *cluster, const float *dy, const float *x,
+                                   const float *gate, float *dx, float *dgate);
 /* Periodic structures -> neighbour graphs on the device, a batch per call (periodic_graph.hip).  It replaces get_graph_from_basis
  * of the reference's chemical examples (example/example_library/src/mod_read_chemical_graphs.f90:196-278); the step in front of
  * athena_mp_graph_create_from_edges_dev.
