@@ -46,6 +46,7 @@
 
 #include <algorithm>
 
+#include "call_scratch.h"
 #include "cell_grid.h"
 #include "common.h"
 #include "radius_cells.h"
@@ -270,13 +271,15 @@ int radius_pairs_bipartite_core(const char *who, int32_t B, int32_t nq, const in
     // the queries in the order of their cell: one key pass, one stable pass of the sort
     uint32_t *d_qkey = nullptr, *d_qkey_s = nullptr, *d_qkey_t = nullptr, *d_count = nullptr;
     int32_t *d_qperm = nullptr, *d_qperm_t = nullptr;
-    void *d_temp = nullptr;
+    char *d_temp = nullptr;
     unsigned long long *d_tile = nullptr, *d_offset = nullptr;
     long long *d_edge_off = nullptr;
-    if (tmp.get(&d_qkey, nq) || tmp.get(&d_qkey_s, nq) || tmp.get(&d_qkey_t, nq) || tmp.get(&d_qperm, nq) || tmp.get(&d_qperm_t, nq) ||
-        tmp.get((char **)&d_temp, radix::scratch_bytes(nq)) || tmp.get(&d_count, nq) ||
-        tmp.get(&d_tile, (size_t)scan64::tiles(nq) + 1) || tmp.get(&d_offset, nq) || tmp.get(&d_edge_off, (size_t)B + 1))
-        return 1;
+    const size_t NQ = (size_t)nq;
+    Pieces pc;
+    pc.add(&d_qkey, NQ), pc.add(&d_qkey_s, NQ), pc.add(&d_qkey_t, NQ), pc.add(&d_qperm, NQ), pc.add(&d_qperm_t, NQ);
+    pc.add(&d_temp, radix::scratch_bytes(nq)), pc.add(&d_count, NQ), pc.add(&d_tile, (size_t)scan64::tiles(nq) + 1), pc.add(&d_offset, NQ);
+    pc.add(&d_edge_off, (size_t)B + 1);
+    if (tmp.carve(pc)) return 1;
     hipLaunchKernelGGL(bip_query_key_kernel, dim3(qit.item_blocks), dim3(64 * kItemWaves), 0, st, qit.W, (const int32_t *)qit.d_items,
                        (int)dim, queries_dev, (const Grid *)cg.d_grids, (const uint32_t *)cg.d_cell_base, d_qkey);
     AMP_LAUNCH_CHECK();
@@ -312,10 +315,11 @@ int radius_pairs_bipartite_core(const char *who, int32_t B, int32_t nq, const in
     const int64_t E = (int64_t)total;
     unsigned long long *d_pk = nullptr, *d_pk_s = nullptr, *d_pk_t = nullptr;
     int32_t *d_v = nullptr, *d_v_t = nullptr;
-    void *d_temp2 = nullptr;
-    if (tmp.get(&d_pk, E) || tmp.get(&d_pk_s, E) || tmp.get(&d_pk_t, E) || tmp.get(&d_v, E) || tmp.get(&d_v_t, E) ||
-        tmp.get((char **)&d_temp2, radix::scratch_bytes(E)))
-        return 1;
+    char *d_temp2 = nullptr;
+    const size_t EE = (size_t)E;
+    Pieces pk;
+    pk.add(&d_pk, EE), pk.add(&d_pk_s, EE), pk.add(&d_pk_t, EE), pk.add(&d_v, EE), pk.add(&d_v_t, EE), pk.add(&d_temp2, radix::scratch_bytes(E));
+    if (tmp.carve(pk)) return 1;
     launch_bip_neighbour<true>(dim, nq, st, B, d_qoff, d_soff, (const Grid *)cg.d_grids, (const uint32_t *)cg.d_cell_base, M, r2,
                                queries_dev, (const int32_t *)d_qperm, (const float *)cg.d_sorted, (const int32_t *)cg.d_perm,
                                (const int32_t *)cg.d_cell_start, (uint32_t *)nullptr, (const unsigned long long *)d_offset, d_pk);
@@ -348,22 +352,19 @@ int bipartite_csr_from_pairs(const char *who, int32_t n_rows, int32_t n_cols, in
     hipStream_t st = stream();
     Scratch tmp;
     int32_t *d_ia = nullptr, *d_cdeg = nullptr, *d_ja = nullptr;
-    unsigned long long *d_bad = nullptr;
-    if (tmp.get(&d_ia, (size_t)n_rows + 1) || tmp.get(&d_cdeg, n_cols) || tmp.get(&d_bad, 1)) return 1;
+    BadWord word;
+    if (tmp.get(&d_ia, (size_t)n_rows + 1) || tmp.get(&d_cdeg, n_cols) || word.arm(tmp, st)) return 1;
     AMP_HIP(hipMalloc((void **)&d_ja, sizeof(int32_t) * 2 * (size_t)std::max<int64_t>(n_pairs, 1)));
     *ja_dev = d_ja;                                                    // the caller frees it on every path from here
-    const unsigned long long none = ~0ull;
-    AMP_HIP(hipMemcpyAsync(d_bad, &none, sizeof(none), hipMemcpyHostToDevice, st));
     AMP_HIP(hipMemsetAsync(d_cdeg, 0, sizeof(int32_t) * (size_t)std::max(n_cols, 1), st));
     if (n_pairs > 0) {
         hipLaunchKernelGGL(bip_entries_kernel, dim3(blocks(n_pairs)), dim3(256), 0, st, n_pairs, pairs_dev, n_rows, n_cols, d_ja, d_cdeg,
-                           d_bad);
+                           word.dev);
         AMP_LAUNCH_CHECK();
     }
-    unsigned long long bad = none;
-    AMP_HIP(hipMemcpyAsync(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost, st));
-    AMP_HIP(hipStreamSynchronize(st));
-    if (bad != none) {
+    unsigned long long bad = ~0ull;
+    if (int rc = word.fetch(&bad, st)) return rc;
+    if (bad != ~0ull) {
         int32_t p[4] = {0, 0, 0, 0};                                   // the pair in front of it and the pair itself
         const unsigned long long from = bad > 0 ? bad - 1 : bad;
         AMP_HIP(hipMemcpy(p + 2 * (from == bad), pairs_dev + 2 * from, sizeof(int32_t) * 2 * (size_t)(bad - from + 1), hipMemcpyDeviceToHost));
@@ -417,9 +418,7 @@ extern "C" int athena_mp_radius_graph_bipartite_host(int32_t n_clouds, int32_t n
     hipStream_t st = amp::stream();
     amp::Scratch tmp;
     float *d_q = nullptr, *d_s = nullptr;
-    if (tmp.get(&d_q, (size_t)n_queries * dim) || tmp.get(&d_s, (size_t)n_sources * dim)) return 1;
-    if (n_queries > 0) AMP_HIP(hipMemcpyAsync(d_q, queries_host, sizeof(float) * (size_t)n_queries * dim, hipMemcpyHostToDevice, st));
-    if (n_sources > 0) AMP_HIP(hipMemcpyAsync(d_s, sources_host, sizeof(float) * (size_t)n_sources * dim, hipMemcpyHostToDevice, st));
+    if (tmp.upload(&d_q, queries_host, (size_t)n_queries * dim, st) || tmp.upload(&d_s, sources_host, (size_t)n_sources * dim, st)) return 1;
     int64_t E = 0;
     if (int rc = amp::radius_pairs_bipartite_core(who, n_clouds, n_queries, query_offsets_host, n_sources, source_offsets_host, dim, d_q,
                                                   d_s, radius, nullptr, nullptr, 0, nullptr, edge_offsets_out, &E))
@@ -435,7 +434,7 @@ extern "C" int athena_mp_radius_graph_bipartite_host(int32_t n_clouds, int32_t n
     if (int rc = amp::radius_pairs_bipartite_core(who, n_clouds, n_queries, query_offsets_host, n_sources, source_offsets_host, dim, d_q,
                                                   d_s, radius, d_pairs, d_coords, E, nullptr, edge_offsets_out, &E))
         return rc;
-    if (E > 0) AMP_HIP(hipMemcpyAsync(coords_out, d_coords, sizeof(float) * (size_t)E * dim, hipMemcpyDeviceToHost, st));
+    if (tmp.download(coords_out, d_coords, (size_t)E * dim, st)) return 1;
     int32_t *ja_dev = nullptr;
     std::vector<int32_t> row_deg, col_deg;
     const int rc = amp::bipartite_csr_from_pairs(who, n_queries, n_sources, E, d_pairs, adj_ia_out, adj_ja_out, capacity, &ja_dev, &row_deg,

@@ -21,7 +21,7 @@ __global__ __launch_bounds__(256) void rg_cell_start_kernel(uint32_t n_cells, co
     cell_start[c] = lo;
 }
 
-inline unsigned blocks(int64_t n) { return (unsigned)((n + 255) / 256); }
+inline unsigned blocks(int64_t n, int per = 256) { return (unsigned)((n + per - 1) / per); }
 inline int bits_for(unsigned long long max_value)
 {
     int b = 1;

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/athena_mp.h"
+#include "pieces.h"
 
 namespace amp {
 
@@ -72,6 +73,26 @@ struct Scratch {
     {
         AMP_HIP(hipMalloc((void **)p, sizeof(T) * (count ? count : 1)));
         ptrs.push_back(*p);
+        return 0;
+    }
+    // every array of the list out of one allocation (pieces.h)
+    int carve(Pieces &pc)
+    {
+        char *base = nullptr;
+        if (get(&base, pc.bytes())) return 1;
+        pc.place(base);
+        return 0;
+    }
+    // host staging of the *_host entries: an input array up (null or empty: allocated, not copied), an output array home
+    template <typename T> int upload(T **dev, const T *host, size_t count, hipStream_t st)
+    {
+        if (get(dev, count)) return 1;
+        if (host && count > 0) AMP_HIP(hipMemcpyAsync(*dev, host, sizeof(T) * count, hipMemcpyHostToDevice, st));
+        return 0;
+    }
+    template <typename T> static int download(T *host, const T *dev, size_t count, hipStream_t st)
+    {
+        if (host && dev && count > 0) AMP_HIP(hipMemcpyAsync(host, dev, sizeof(T) * count, hipMemcpyDeviceToHost, st));
         return 0;
     }
     ~Scratch()

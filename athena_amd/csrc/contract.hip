@@ -28,13 +28,14 @@
 //   ck_flag_kernel      8 / 20 / 0 / 0 / 8
 //   ck_start_kernel     4 / 16 / 0 / 0 / 8
 //   ck_fill_kernel     28 / 34 / 0 / 0 / 8
-//   ck_longest_kernel  20 / 32 / 0 / 0 / 8
+//   longest_row_kernel of call_scratch.h (the largest coarse pair of the stats)
 //   gp_pairs_kernel     8 / 18 / 0 / 0 / 8
 //   cp_cells_kernel    13 / 29 / 0 / 0 / 8
 #include <string.h>
 
 #include <algorithm>
 
+#include "call_scratch.h"
 #include "cell_start.h"
 #include "common.h"
 #include "radix_sort.h"
@@ -45,8 +46,6 @@ int64_t g_contract_stats[4] = {0, 0, 0, 0};             // athena_mp_contract_st
 }
 
 namespace {
-
-constexpr int kCkMaxBlocks = 512;            // blocks of ck_longest_kernel; one partial per wave
 
 // two int32 that travel as 8 bytes; alignment 4, which is all a caller's pointer has to have
 struct Pair {
@@ -154,16 +153,6 @@ __global__ __launch_bounds__(256) void ck_fill_kernel(int64_t E, int32_t P, int3
         for (int c = 0; c < dim; ++c) coords[(int64_t)(id - 1) * dim + c] = row_points[(int64_t)(a - 1) * dim + c] - col_points[(int64_t)(b - 1) * dim + c];
 }
 
-// the largest difference of start [P + 1]: one partial per wave, folded on the host
-__global__ __launch_bounds__(256) void ck_longest_kernel(int32_t P, const int32_t *__restrict__ start, int32_t *__restrict__ partial)
-{
-    int32_t best = 0;
-    for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < P; r += (int64_t)gridDim.x * 256) best = max(best, start[r + 1] - start[r]);
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) best = max(best, __shfl_xor(best, d, 64));
-    if ((threadIdx.x & 63) == 0) partial[blockIdx.x * 4 + (threadIdx.x >> 6)] = best;
-}
-
 // one lane per edge column of a handle: (row + 1, col + 1) of the first entry that carries it, (0, 0) where none does
 __global__ __launch_bounds__(256) void gp_pairs_kernel(int32_t n_edge_cols, const int32_t *__restrict__ e_rowptr, const int32_t *__restrict__ e_row,
                                                        const int32_t *__restrict__ e_col, const int32_t *__restrict__ col, int32_t *__restrict__ pairs)
@@ -249,28 +238,21 @@ int contract_pairs_core(const char *who, int64_t E, const int32_t *pairs_dev, in
     const int ba = bits_for((unsigned long long)m_rows), bb = bits_for((unsigned long long)m_cols), bits = ba + bb + 1;
     const unsigned long long out = 1ull << (ba + bb);
 
-    // one allocation cut into pieces
-    size_t total = 0;
-    auto piece = [&](size_t bytes) {
-        const size_t at = total;
-        total += (bytes + 255) & ~(size_t)255;
-        return at;
-    };
+    // one allocation cut into pieces (pieces.h)
     const size_t N = (size_t)E;
-    const size_t o_info = piece(sizeof(Info)), o_key = piece(8 * N), o_key_s = piece(8 * N), o_key_t = piece(8 * N), o_before = piece(8 * N),
-                 o_tile = piece(8 * ((size_t)scan64::tiles(E) + 1)), o_perm = piece(4 * N), o_perm_t = piece(4 * N), o_flag = piece(4 * N),
-                 o_start = piece(4 * (N + 1)), o_longest = piece(4 * 4 * (size_t)kCkMaxBlocks), o_temp = piece(radix::scratch_bytes(E));
+    Info *d_info = nullptr;
+    unsigned long long *d_key = nullptr, *d_key_s = nullptr, *d_key_t = nullptr, *d_before = nullptr, *d_tile = nullptr;
+    int32_t *d_perm = nullptr, *d_perm_t = nullptr, *d_start = nullptr, *d_longest = nullptr;
+    uint32_t *d_flag = nullptr;
+    char *d_temp = nullptr;
+    Pieces pc;
+    pc.add(&d_info, 1), pc.add(&d_key, N), pc.add(&d_key_s, N), pc.add(&d_key_t, N), pc.add(&d_before, N);
+    pc.add(&d_tile, (size_t)scan64::tiles(E) + 1), pc.add(&d_perm, N), pc.add(&d_perm_t, N), pc.add(&d_flag, N), pc.add(&d_start, N + 1);
+    // longest_row uses kLongestBlocks words; four times that keeps the request what it was when the partials were one per wave
+    // (tests/test_pieces.py holds bytes() to it)
+    pc.add(&d_longest, 4 * (size_t)kLongestBlocks), pc.add(&d_temp, radix::scratch_bytes(E));
     Scratch tmp;
-    char *base = nullptr;
-    if (tmp.get(&base, total)) return 1;
-    Info *d_info = (Info *)(base + o_info);
-    unsigned long long *d_key = (unsigned long long *)(base + o_key), *d_key_s = (unsigned long long *)(base + o_key_s),
-                       *d_key_t = (unsigned long long *)(base + o_key_t), *d_before = (unsigned long long *)(base + o_before),
-                       *d_tile = (unsigned long long *)(base + o_tile);
-    int32_t *d_perm = (int32_t *)(base + o_perm), *d_perm_t = (int32_t *)(base + o_perm_t), *d_start = (int32_t *)(base + o_start),
-            *d_longest = (int32_t *)(base + o_longest);
-    uint32_t *d_flag = (uint32_t *)(base + o_flag);
-    void *d_temp = base + o_temp;
+    if (tmp.carve(pc)) return 1;
 
     Info info{(unsigned long long)E, ~0ull, ~0ull, ~0ull};
     AMP_HIP(hipMemcpyAsync(d_info, &info, sizeof(Info), hipMemcpyHostToDevice, st));
@@ -323,13 +305,9 @@ int contract_pairs_core(const char *who, int64_t E, const int32_t *pairs_dev, in
     hipLaunchKernelGGL(ck_fill_kernel, dim3(blocks(E + 1)), dim3(256), 0, st, E, P, M, bb, (int)dim, (const unsigned long long *)d_key_s,
                        (const int32_t *)d_perm, (const uint32_t *)d_flag, (const unsigned long long *)d_before, (const int32_t *)d_start,
                        row_points_dev, col_points_dev, coarse_pairs_dev, rowptr_dev, members_dev, weights_dev, edge_pair_dev, coords_dev);
-    const int longest_blocks = (int)std::max<int64_t>(1, std::min<int64_t>(kCkMaxBlocks, blocks(P)));
-    hipLaunchKernelGGL(ck_longest_kernel, dim3(longest_blocks), dim3(256), 0, st, P, (const int32_t *)d_start, d_longest);
-    AMP_LAUNCH_CHECK();
-    std::vector<int32_t> longest((size_t)longest_blocks * 4);
-    AMP_HIP(hipMemcpyAsync(longest.data(), d_longest, sizeof(int32_t) * longest.size(), hipMemcpyDeviceToHost, st));
-    AMP_HIP(hipStreamSynchronize(st));                                // scratch dies with this scope
-    g_contract_stats[3] = *std::max_element(longest.begin(), longest.end());
+    int32_t longest = 0;
+    if (int rc = longest_row(P, (const int32_t *)d_start, d_longest, &longest, st)) return rc;   // the wait; scratch dies with this scope
+    g_contract_stats[3] = longest;
     return 0;
 }
 
@@ -368,26 +346,12 @@ extern "C" int athena_mp_contract_pairs_host(int64_t n_pairs, const int32_t *pai
     const bool one_map = row_cluster && row_cluster == col_cluster, one_set = row_points && row_points == col_points;
     int32_t *d_pairs = nullptr, *d_rc = nullptr, *d_cc = nullptr, *d_cp = nullptr, *d_rowptr = nullptr, *d_mem = nullptr, *d_ep = nullptr;
     float *d_rp = nullptr, *d_cpt = nullptr, *d_w = nullptr, *d_co = nullptr;
-    if (tmp.get(&d_pairs, 2 * N)) return 1;
-    if (N > 0) AMP_HIP(hipMemcpyAsync(d_pairs, pairs, sizeof(int32_t) * 2 * N, hipMemcpyHostToDevice, st));
-    if (row_cluster) {
-        if (tmp.get(&d_rc, (size_t)n_rows)) return 1;
-        if (n_rows > 0) AMP_HIP(hipMemcpyAsync(d_rc, row_cluster, sizeof(int32_t) * (size_t)n_rows, hipMemcpyHostToDevice, st));
-    }
+    if (tmp.upload(&d_pairs, pairs, 2 * N, st) || (row_cluster && tmp.upload(&d_rc, row_cluster, (size_t)n_rows, st))) return 1;
     if (one_map) d_cc = d_rc;
-    else if (col_cluster) {
-        if (tmp.get(&d_cc, (size_t)n_cols)) return 1;
-        if (n_cols > 0) AMP_HIP(hipMemcpyAsync(d_cc, col_cluster, sizeof(int32_t) * (size_t)n_cols, hipMemcpyHostToDevice, st));
-    }
-    if (row_points) {
-        if (tmp.get(&d_rp, (size_t)m_rows * D)) return 1;
-        if (m_rows > 0) AMP_HIP(hipMemcpyAsync(d_rp, row_points, sizeof(float) * (size_t)m_rows * D, hipMemcpyHostToDevice, st));
-    }
+    else if (col_cluster && tmp.upload(&d_cc, col_cluster, (size_t)n_cols, st)) return 1;
+    if (row_points && tmp.upload(&d_rp, row_points, (size_t)m_rows * D, st)) return 1;
     if (one_set) d_cpt = d_rp;
-    else if (col_points) {
-        if (tmp.get(&d_cpt, (size_t)m_cols * D)) return 1;
-        if (m_cols > 0) AMP_HIP(hipMemcpyAsync(d_cpt, col_points, sizeof(float) * (size_t)m_cols * D, hipMemcpyHostToDevice, st));
-    }
+    else if (col_points && tmp.upload(&d_cpt, col_points, (size_t)m_cols * D, st)) return 1;
     if ((coarse_pairs_out && tmp.get(&d_cp, 2 * N)) || (rowptr_out && tmp.get(&d_rowptr, N + 1)) || (members_out && tmp.get(&d_mem, 2 * N)) ||
         (weights_out && tmp.get(&d_w, N)) || (edge_pair_out && tmp.get(&d_ep, N)) || (coords_out && tmp.get(&d_co, N * D)))
         return 1;
@@ -401,12 +365,10 @@ extern "C" int athena_mp_contract_pairs_host(int64_t n_pairs, const int32_t *pai
                 (long long)capacity, (long long)P);
     AMP_REQUIRE(!(members_out || weights_out) || member_capacity >= M, "%s: the buffers hold %lld members, the list has %lld", who,
                 (long long)member_capacity, (long long)M);
-    if (d_cp && P > 0) AMP_HIP(hipMemcpyAsync(coarse_pairs_out, d_cp, sizeof(int32_t) * 2 * (size_t)P, hipMemcpyDeviceToHost, st));
-    if (d_rowptr) AMP_HIP(hipMemcpyAsync(rowptr_out, d_rowptr, sizeof(int32_t) * ((size_t)P + 1), hipMemcpyDeviceToHost, st));
-    if (d_mem && M > 0) AMP_HIP(hipMemcpyAsync(members_out, d_mem, sizeof(int32_t) * 2 * (size_t)M, hipMemcpyDeviceToHost, st));
-    if (d_w && M > 0) AMP_HIP(hipMemcpyAsync(weights_out, d_w, sizeof(float) * (size_t)M, hipMemcpyDeviceToHost, st));
-    if (d_ep && N > 0) AMP_HIP(hipMemcpyAsync(edge_pair_out, d_ep, sizeof(int32_t) * N, hipMemcpyDeviceToHost, st));
-    if (d_co && P > 0) AMP_HIP(hipMemcpyAsync(coords_out, d_co, sizeof(float) * (size_t)P * D, hipMemcpyDeviceToHost, st));
+    if (tmp.download(coarse_pairs_out, d_cp, 2 * (size_t)P, st) || tmp.download(rowptr_out, d_rowptr, (size_t)P + 1, st) ||
+        tmp.download(members_out, d_mem, 2 * (size_t)M, st) || tmp.download(weights_out, d_w, (size_t)M, st) ||
+        tmp.download(edge_pair_out, d_ep, N, st) || tmp.download(coords_out, d_co, (size_t)P * D, st))
+        return 1;
     AMP_HIP(hipStreamSynchronize(st));
     return 0;
 }
@@ -452,14 +414,13 @@ extern "C" int athena_mp_cell_pairs(int32_t n_vertices, int64_t n_cells, int32_t
                 (long long)total);
     hipStream_t st = amp::stream();
     amp::Scratch tmp;
-    unsigned long long *d_bad = nullptr, bad = ~0ull;
-    if (tmp.get(&d_bad, 1)) return 1;
-    AMP_HIP(hipMemcpyAsync(d_bad, &bad, sizeof(bad), hipMemcpyHostToDevice, st));
+    BadWord word;
+    unsigned long long bad = ~0ull;
+    if (int rc = word.arm(tmp, st)) return rc;
     hipLaunchKernelGGL(cp_cells_kernel, dim3(blocks(total)), dim3(256), 0, st, total, nv, ne, cell_code(cell_type), n_vertices, cells_dev, pairs_dev,
-                       d_bad);
+                       word.dev);
     AMP_LAUNCH_CHECK();
-    AMP_HIP(hipMemcpyAsync(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost, st));
-    AMP_HIP(hipStreamSynchronize(st));
+    if (int rc = word.fetch(&bad, st)) return rc;
     if (bad != ~0ull) {
         int32_t c[4] = {0, 0, 0, 0};
         AMP_HIP(hipMemcpy(c, cells_dev + bad * nv, sizeof(int32_t) * nv, hipMemcpyDeviceToHost));

@@ -459,9 +459,9 @@ int farthest_points_core(const char *who, int32_t B, int32_t n, const int32_t *o
     if (n_str > 0) {
         float *d_dmin = nullptr, *d_box = nullptr;
         unsigned long long *d_ckey = nullptr, *d_stats = nullptr;
-        if (tmp.get(&d_dmin, n) || tmp.get(&d_box, 6 * (size_t)n_chunks) || tmp.get(&d_ckey, (size_t)n_chunks) ||
-            tmp.get(&d_stats, 2 * n_str))
-            return 1;
+        Pieces pc;
+        pc.add(&d_dmin, (size_t)n), pc.add(&d_box, 6 * (size_t)n_chunks), pc.add(&d_ckey, (size_t)n_chunks), pc.add(&d_stats, 2 * n_str);
+        if (tmp.carve(pc)) return 1;
         launch_fps_stream(dim, (int32_t)n_str, st, (const FpsTask *)(d_tasks + n_reg), points_dev, (const float *)cg.d_sorted,
                           (const int32_t *)cg.d_perm, n_chunks, d_dmin, d_box, d_ckey, d_stats, sample_dev, sample_points_dev,
                           sample_sqdist_dev, cover_dev);
@@ -504,17 +504,15 @@ extern "C" int athena_mp_farthest_points_host(int32_t n_clouds, int32_t n, const
     const size_t m = (size_t)n_samples, B = (size_t)n_clouds;
     float *d_p = nullptr, *d_sp = nullptr, *d_sq = nullptr, *d_cover = nullptr;
     int32_t *d_s = nullptr;
-    if (tmp.get(&d_p, (size_t)n * dim) || (sample_out && tmp.get(&d_s, m)) || (sample_points_out && tmp.get(&d_sp, m * dim)) ||
+    if (tmp.upload(&d_p, points_host, (size_t)n * dim, st) || (sample_out && tmp.get(&d_s, m)) || (sample_points_out && tmp.get(&d_sp, m * dim)) ||
         (sample_sqdist_out && tmp.get(&d_sq, m)) || (cover_sqdist_out && tmp.get(&d_cover, B)))
         return 1;
-    if (n > 0) AMP_HIP(hipMemcpyAsync(d_p, points_host, sizeof(float) * (size_t)n * dim, hipMemcpyHostToDevice, st));
     if (int rc = amp::farthest_points_core(who, n_clouds, n, offsets_host, dim, d_p, n_samples, sample_offsets_host, start_host, d_s, d_sp,
                                            d_sq, d_cover))
         return rc;
-    if (d_s && m > 0) AMP_HIP(hipMemcpyAsync(sample_out, d_s, sizeof(int32_t) * m, hipMemcpyDeviceToHost, st));
-    if (d_sp && m > 0) AMP_HIP(hipMemcpyAsync(sample_points_out, d_sp, sizeof(float) * m * dim, hipMemcpyDeviceToHost, st));
-    if (d_sq && m > 0) AMP_HIP(hipMemcpyAsync(sample_sqdist_out, d_sq, sizeof(float) * m, hipMemcpyDeviceToHost, st));
-    if (d_cover && B > 0) AMP_HIP(hipMemcpyAsync(cover_sqdist_out, d_cover, sizeof(float) * B, hipMemcpyDeviceToHost, st));
+    if (tmp.download(sample_out, d_s, m, st) || tmp.download(sample_points_out, d_sp, m * dim, st) || tmp.download(sample_sqdist_out, d_sq, m, st) ||
+        tmp.download(cover_sqdist_out, d_cover, B, st))
+        return 1;
     AMP_HIP(hipStreamSynchronize(st));
     return 0;
 }

@@ -15,6 +15,7 @@
 
 #include <algorithm>
 
+#include "cell_start.h"
 #include "common.h"
 #include "radix_sort.h"
 
@@ -100,7 +101,7 @@ __global__ void gather_e_kernel(int64_t n_with, int64_t n_none, const int32_t *_
     e_row[q] = row_of[w];
 }
 
-inline unsigned blocks(int64_t n) { return (unsigned)((n + 255) / 256); }
+// not cell_start.h's: at least 1, at most 31
 inline int bits_for(int64_t max_value)
 {
     int b = 1;
@@ -164,6 +165,8 @@ int graph_build_device(athena_mp_graph *g, const int32_t *adj_ja, const std::vec
             *d_ekey = nullptr, *d_rank_r = nullptr, *d_rank_c = nullptr;
     float *d_table = nullptr;
     BadEntry *d_bad = nullptr;
+    // an allocation per array, not one carved (pieces.h): carved, the sampler's block handles of 1024 seeds were slower to build
+    // (profiles/call_scratch_ab.txt)
     if ((adj_ja_dev == nullptr && tmp.get(&d_ja, 2 * (size_t)nnz)) || tmp.get(&d_row_of, nnz) || tmp.get(&d_perm, nnz) ||
         tmp.get(&d_keys_sorted, nnz) || tmp.get(&d_tmp_k, nnz) || tmp.get(&d_tmp_v, nnz) || tmp.get(&d_rank_r, rank_r.size()) || tmp.get(&d_rank_c, rank_c.size()) ||
         tmp.get(&d_table, table.size()) || tmp.get(&d_bad, 1))
@@ -239,7 +242,7 @@ int graph_build_device(athena_mp_graph *g, const int32_t *adj_ja, const std::vec
     // ---- edge-column index: stable sort of the entries by edge id, entries without one in front --------
     int64_t n_with = 0;
     if (n_edge_cols > 0 && nnz > 0) {
-        if (int rc = radix::sort_pairs<uint32_t>((const uint32_t *)d_ekey, nullptr, nnz, bits_for(n_edge_cols), (uint32_t *)d_keys_sorted,
+        if (int rc = radix::sort_pairs<uint32_t>((const uint32_t *)d_ekey, nullptr, nnz, bits_for((int64_t)n_edge_cols), (uint32_t *)d_keys_sorted,
                                                  d_perm, (uint32_t *)d_tmp_k, d_tmp_v, d_temp, st))
             return rc;
         // e_rowptr[e] = lower_bound(key >= e + 1) - n_none; computed in two steps: first the raw positions
@@ -361,10 +364,12 @@ int csr_from_edges_core(int32_t n_vertices, int64_t n_pairs, const int32_t *inde
     Scratch tmp;
     int32_t *d_pairs = nullptr, *d_dst = nullptr, *d_dst_s = nullptr, *d_dst_t = nullptr, *d_loop = nullptr, *d_ia = nullptr, *d_ja = nullptr;
     unsigned long long *d_keys = nullptr, *d_keys_s = nullptr, *d_keys_t = nullptr, *d_bad = nullptr;
-    if ((!list_on_device && tmp.get(&d_pairs, 2 * (size_t)n_pairs)) || tmp.get(&d_dst, total) || tmp.get(&d_dst_s, total) || tmp.get(&d_dst_t, total) ||
-        tmp.get(&d_loop, n_vertices) || tmp.get(&d_ia, (size_t)n_vertices + 1) || tmp.get(&d_keys, total) ||
-        tmp.get(&d_keys_s, total) || tmp.get(&d_keys_t, total) || tmp.get(&d_bad, 1))
-        return 1;
+    const size_t TT = (size_t)total;
+    Pieces pc;
+    if (!list_on_device) pc.add(&d_pairs, 2 * (size_t)n_pairs);
+    pc.add(&d_dst, TT), pc.add(&d_dst_s, TT), pc.add(&d_dst_t, TT), pc.add(&d_loop, (size_t)std::max(n_vertices, 1));
+    pc.add(&d_ia, (size_t)n_vertices + 1), pc.add(&d_keys, TT), pc.add(&d_keys_s, TT), pc.add(&d_keys_t, TT), pc.add(&d_bad, 1);
+    if (tmp.carve(pc)) return 1;
     const unsigned long long none = ~0ull;
     AMP_HIP(hipMemcpyAsync(d_bad, &none, sizeof(none), hipMemcpyHostToDevice, st));
     AMP_HIP(hipMemsetAsync(d_loop, 0, sizeof(int32_t) * (size_t)std::max(n_vertices, 1), st));

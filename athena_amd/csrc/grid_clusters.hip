@@ -33,6 +33,7 @@
 
 #include <algorithm>
 
+#include "call_scratch.h"
 #include "cell_grid.h"
 #include "common.h"
 #include "knn_cells.h"
@@ -47,7 +48,6 @@ int64_t g_grid_clusters_stats[4] = {0, 0, 0, 0};       // athena_mp_grid_cluster
 namespace {
 
 constexpr int kGcG = 4;                      // lanes per cluster
-constexpr int kGcMaxBlocks = 512;            // block partials of the largest cluster
 constexpr float kGcMaxCellsAxis = 2097152.f; // 2^21
 
 // one wave per work item (cloud, p0, p1): key = (cloud << cbits) | the cell in the cloud's own grid, c_0 fastest
@@ -96,19 +96,6 @@ __global__ __launch_bounds__(256) void gc_fill_kernel(int32_t n, int32_t m, cons
         pairs[2 * s + 1] = j + 1;
     }
     if (head) rowptr[id - 1] = (int32_t)s;
-}
-
-// the largest row of rowptr [m + 1]: block partials, folded on the host
-__global__ __launch_bounds__(256) void gc_longest_kernel(int32_t m, const int32_t *__restrict__ rowptr, int32_t *__restrict__ partial)
-{
-    __shared__ int32_t part[4];
-    int32_t best = 0;
-    for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < m; r += (int64_t)gridDim.x * 256) best = max(best, rowptr[r + 1] - rowptr[r]);
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) best = max(best, __shfl_xor(best, d, 64));
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = best;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = max(max(part[0], part[1]), max(part[2], part[3]));
 }
 
 // G = 4 lanes per cluster (header).  sorted / perm / key_s are in key order: cluster r is the slots rowptr[r] .. rowptr[r + 1] - 1.
@@ -292,29 +279,20 @@ int grid_clusters_core(const char *who, int32_t B, int32_t n, const int32_t *off
     AMP_REQUIRE(cbits + bbits <= 62, "%s: the keys need %d + %d bits for %d clouds and %llu cells, more than 62", who, bbits, cbits, B, cells_max);
     const int bits = cbits + bbits;
 
-    // one allocation cut into pieces: a hipMalloc and a hipFree per array would be most of a call's time
-    size_t total = 0;
-    auto piece = [&](size_t bytes) {
-        const size_t at = total;
-        total += (bytes + 255) & ~(size_t)255;
-        return at;
-    };
+    // one allocation cut into pieces (pieces.h): a hipMalloc and a hipFree per array would be most of a call's time
     const size_t N = (size_t)n;
-    const size_t o_grids = piece(sizeof(Grid) * (size_t)B), o_key = piece(8 * N), o_key_s = piece(8 * N), o_key_t = piece(8 * N),
-                 o_before = piece(8 * N), o_tile = piece(8 * ((size_t)scan64::tiles(n) + 1)), o_coff = piece(8 * ((size_t)B + 1)),
-                 o_perm = piece(4 * N), o_perm_t = piece(4 * N), o_flag = piece(4 * N), o_sorted = piece(4 * N * dim),
-                 o_rowptr = piece(4 * (N + 1)), o_longest = piece(4 * (size_t)kGcMaxBlocks), o_temp = piece(radix::scratch_bytes(n));
-    char *base = nullptr;
-    if (tmp.get(&base, total)) return 1;
-    Grid *d_grids = (Grid *)(base + o_grids);
-    unsigned long long *d_key = (unsigned long long *)(base + o_key), *d_key_s = (unsigned long long *)(base + o_key_s),
-                       *d_key_t = (unsigned long long *)(base + o_key_t), *d_before = (unsigned long long *)(base + o_before),
-                       *d_tile = (unsigned long long *)(base + o_tile);
-    long long *d_coff = (long long *)(base + o_coff);
-    int32_t *d_perm = (int32_t *)(base + o_perm), *d_perm_t = (int32_t *)(base + o_perm_t), *d_longest = (int32_t *)(base + o_longest);
-    uint32_t *d_flag = (uint32_t *)(base + o_flag);
-    float *d_sorted = (float *)(base + o_sorted);
-    void *d_temp = base + o_temp;
+    Grid *d_grids = nullptr;
+    unsigned long long *d_key = nullptr, *d_key_s = nullptr, *d_key_t = nullptr, *d_before = nullptr, *d_tile = nullptr;
+    long long *d_coff = nullptr;
+    int32_t *d_perm = nullptr, *d_perm_t = nullptr, *d_rowptr = nullptr, *d_longest = nullptr;
+    uint32_t *d_flag = nullptr;
+    float *d_sorted = nullptr;
+    char *d_temp = nullptr;
+    Pieces pc;
+    pc.add(&d_grids, (size_t)B), pc.add(&d_key, N), pc.add(&d_key_s, N), pc.add(&d_key_t, N), pc.add(&d_before, N);
+    pc.add(&d_tile, (size_t)scan64::tiles(n) + 1), pc.add(&d_coff, (size_t)B + 1), pc.add(&d_perm, N), pc.add(&d_perm_t, N), pc.add(&d_flag, N);
+    pc.add(&d_sorted, N * dim), pc.add(&d_rowptr, N + 1), pc.add(&d_longest, (size_t)kLongestBlocks), pc.add(&d_temp, radix::scratch_bytes(n));
+    if (tmp.carve(pc)) return 1;
     AMP_HIP(hipMemcpyAsync(d_grids, grids.data(), sizeof(Grid) * (size_t)B, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(gc_key_kernel, dim3(it.item_blocks), dim3(64 * kItemWaves), 0, st, it.W, (const int32_t *)it.d_items, (int)dim, points_dev,
                        (const Grid *)d_grids, cbits, d_key);
@@ -342,21 +320,17 @@ int grid_clusters_core(const char *who, int32_t B, int32_t n, const int32_t *off
     AMP_REQUIRE(capacity >= m64, "%s: the buffers hold %lld clusters, the batch has %lld", who, (long long)capacity, (long long)m64);
     const int32_t m = (int32_t)m64;
 
-    int32_t *d_rowptr = rowptr_dev ? rowptr_dev : (int32_t *)(base + o_rowptr);
-    const int longest_blocks = (int)std::min<int64_t>(kGcMaxBlocks, blocks(m));
+    if (rowptr_dev) d_rowptr = rowptr_dev;
     hipLaunchKernelGGL(gc_fill_kernel, dim3(blocks((int64_t)n + 1)), dim3(256), 0, st, n, m, (const uint32_t *)d_flag,
                        (const unsigned long long *)d_before, (const int32_t *)d_perm, cluster_dev, pairs_dev, d_rowptr);
-    hipLaunchKernelGGL(gc_longest_kernel, dim3(longest_blocks), dim3(256), 0, st, m, (const int32_t *)d_rowptr, d_longest);
     if (weights_dev || centroid_dev || nearest_dev || cell_dev) {
         hipLaunchKernelGGL(rg_gather_points_kernel, dim3(blocks(n)), dim3(256), 0, st, n, (int)dim, points_dev, (const int32_t *)d_perm, d_sorted);
         launch_gc_reduce(dim, m, st, (const int32_t *)d_rowptr, (const float *)d_sorted, (const int32_t *)d_perm,
                          (const unsigned long long *)d_key_s, cbits, (const Grid *)d_grids, weights_dev, centroid_dev, nearest_dev, cell_dev);
     }
-    AMP_LAUNCH_CHECK();
-    std::vector<int32_t> longest((size_t)longest_blocks);
-    AMP_HIP(hipMemcpyAsync(longest.data(), d_longest, sizeof(int32_t) * longest.size(), hipMemcpyDeviceToHost, st));
-    AMP_HIP(hipStreamSynchronize(st));                                // scratch dies with this scope
-    g_grid_clusters_stats[3] = *std::max_element(longest.begin(), longest.end());
+    int32_t longest = 0;
+    if (int rc = longest_row(m, (const int32_t *)d_rowptr, d_longest, &longest, st)) return rc;   // the wait; scratch dies with this scope
+    g_grid_clusters_stats[3] = longest;
     return 0;
 }
 
@@ -369,22 +343,13 @@ int grid_clusters_grad_core(const char *who, int32_t n, int32_t dim, int32_t m, 
     AMP_REQUIRE(cluster_dev && rowptr_dev && dcentroid_dev && dpoints_dev, "%s: null array", who);
     hipStream_t st = stream();
     Scratch tmp;
-    unsigned long long *d_bad = nullptr, bad = ~0ull;
-    if (tmp.get(&d_bad, 1)) return 1;
-    AMP_HIP(hipMemcpyAsync(d_bad, &bad, sizeof(bad), hipMemcpyHostToDevice, st));
+    BadWord bad;
+    if (int rc = bad.arm(tmp, st)) return rc;
     const int64_t total = (int64_t)n * dim;
     hipLaunchKernelGGL(gc_grad_kernel, dim3(blocks(total)), dim3(256), 0, st, total, (int)dim, m, cluster_dev, rowptr_dev, dcentroid_dev,
-                       dpoints_dev, d_bad);
+                       dpoints_dev, bad.dev);
     AMP_LAUNCH_CHECK();
-    AMP_HIP(hipMemcpyAsync(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost, st));
-    AMP_HIP(hipStreamSynchronize(st));
-    if (bad != ~0ull) {
-        int32_t c = 0;
-        AMP_HIP(hipMemcpy(&c, cluster_dev + bad, sizeof(c), hipMemcpyDeviceToHost));
-        set_error("%s: cluster(%llu) = %d outside [1,%d]", who, bad + 1, c, m);
-        return 2;
-    }
-    return 0;
+    return bad.read(who, "cluster", cluster_dev, 1, m, st);
 }
 
 } // namespace amp
@@ -424,8 +389,7 @@ extern "C" int athena_mp_grid_clusters_host(int32_t n_clouds, int32_t n, const i
     const size_t N = (size_t)n;
     float *d_p = nullptr, *d_w = nullptr, *d_c = nullptr;
     int32_t *d_cluster = nullptr, *d_pairs = nullptr, *d_rowptr = nullptr, *d_near = nullptr, *d_cell = nullptr;
-    if (tmp.get(&d_p, N * dim)) return 1;
-    if (n > 0) AMP_HIP(hipMemcpyAsync(d_p, points_host, sizeof(float) * N * dim, hipMemcpyHostToDevice, st));
+    if (tmp.upload(&d_p, points_host, N * dim, st)) return 1;
     const bool fill = adj_ja_out != nullptr;
     if (fill) {
         AMP_REQUIRE(adj_ia_out != nullptr, "%s: null output array", who);
@@ -443,13 +407,10 @@ extern "C" int athena_mp_grid_clusters_host(int32_t n_clouds, int32_t n, const i
     AMP_REQUIRE(capacity >= m, "%s: the buffers hold %lld clusters, the batch has %lld", who, (long long)capacity, (long long)m);
     const size_t M = (size_t)m;
     std::vector<int32_t> pairs(2 * N);
-    AMP_HIP(hipMemcpyAsync(adj_ia_out, d_rowptr, sizeof(int32_t) * (M + 1), hipMemcpyDeviceToHost, st));
-    if (n > 0) AMP_HIP(hipMemcpyAsync(pairs.data(), d_pairs, sizeof(int32_t) * 2 * N, hipMemcpyDeviceToHost, st));
-    if (d_cluster && n > 0) AMP_HIP(hipMemcpyAsync(cluster_out, d_cluster, sizeof(int32_t) * N, hipMemcpyDeviceToHost, st));
-    if (d_w && n > 0) AMP_HIP(hipMemcpyAsync(weights_out, d_w, sizeof(float) * N, hipMemcpyDeviceToHost, st));
-    if (d_c && m > 0) AMP_HIP(hipMemcpyAsync(centroid_out, d_c, sizeof(float) * M * dim, hipMemcpyDeviceToHost, st));
-    if (d_near && m > 0) AMP_HIP(hipMemcpyAsync(nearest_out, d_near, sizeof(int32_t) * M, hipMemcpyDeviceToHost, st));
-    if (d_cell && m > 0) AMP_HIP(hipMemcpyAsync(cell_out, d_cell, sizeof(int32_t) * M * dim, hipMemcpyDeviceToHost, st));
+    if (tmp.download(adj_ia_out, d_rowptr, M + 1, st) || tmp.download(pairs.data(), d_pairs, 2 * N, st) ||
+        tmp.download(cluster_out, d_cluster, N, st) || tmp.download(weights_out, d_w, N, st) || tmp.download(centroid_out, d_c, M * dim, st) ||
+        tmp.download(nearest_out, d_near, M, st) || tmp.download(cell_out, d_cell, M * dim, st))
+        return 1;
     AMP_HIP(hipStreamSynchronize(st));
     for (size_t r = 0; r <= M; ++r) adj_ia_out[r] += 1;              // 1-based
     for (size_t e = 0; e < N; ++e) {                                  // (column, edge id): pair e is entry e
@@ -472,12 +433,11 @@ extern "C" int athena_mp_grid_clusters_grad_host(int32_t n, int32_t dim, int32_t
     const size_t N = (size_t)n, M = (size_t)n_clusters;
     int32_t *d_cluster = nullptr, *d_rowptr = nullptr;
     float *d_dc = nullptr, *d_dp = nullptr;
-    if (tmp.get(&d_cluster, N) || tmp.get(&d_rowptr, M + 1) || tmp.get(&d_dc, M * dim) || tmp.get(&d_dp, N * dim)) return 1;
-    AMP_HIP(hipMemcpyAsync(d_cluster, cluster, sizeof(int32_t) * N, hipMemcpyHostToDevice, st));
-    AMP_HIP(hipMemcpyAsync(d_rowptr, rowptr, sizeof(int32_t) * (M + 1), hipMemcpyHostToDevice, st));
-    if (M > 0) AMP_HIP(hipMemcpyAsync(d_dc, dcentroid, sizeof(float) * M * dim, hipMemcpyHostToDevice, st));
+    if (tmp.upload(&d_cluster, cluster, N, st) || tmp.upload(&d_rowptr, rowptr, M + 1, st) || tmp.upload(&d_dc, dcentroid, M * dim, st) ||
+        tmp.get(&d_dp, N * dim))
+        return 1;
     if (int rc = amp::grid_clusters_grad_core(who, n, dim, n_clusters, d_cluster, d_rowptr, d_dc, d_dp)) return rc;
-    AMP_HIP(hipMemcpyAsync(dpoints, d_dp, sizeof(float) * N * dim, hipMemcpyDeviceToHost, st));
+    if (tmp.download(dpoints, d_dp, N * dim, st)) return 1;
     AMP_HIP(hipStreamSynchronize(st));
     return 0;
 }

@@ -350,16 +350,17 @@ int knn_pairs_bipartite_core(const char *who, int32_t B, int32_t nq, const int32
     // the queries in the order of their centre cell: one key pass, one stable pass of the sort
     uint32_t *d_qkey = nullptr, *d_qkey_s = nullptr, *d_qkey_t = nullptr, *d_count = nullptr, *d_stat = nullptr;
     int32_t *d_qperm = nullptr, *d_qperm_t = nullptr, *d_nbr = nbr_dev;
-    void *d_temp = nullptr;
+    char *d_temp = nullptr;
     unsigned long long *d_tile = nullptr, *d_offset = nullptr, *d_stat_part = nullptr;
     long long *d_edge_off = nullptr;
     WLow *d_wlow = nullptr;
-    if (tmp.get(&d_qkey, nq) || tmp.get(&d_qkey_s, nq) || tmp.get(&d_qkey_t, nq) || tmp.get(&d_qperm, nq) || tmp.get(&d_qperm_t, nq) ||
-        tmp.get((char **)&d_temp, radix::scratch_bytes(nq)) || tmp.get(&d_count, nq) || tmp.get(&d_stat, 3 * (size_t)nq) ||
-        tmp.get(&d_stat_part, 3 * (size_t)kStatBlocks) || tmp.get(&d_tile, (size_t)scan64::tiles(nq) + 1) || tmp.get(&d_offset, nq) ||
-        tmp.get(&d_edge_off, (size_t)B + 1) || tmp.get(&d_wlow, B))
-        return 1;
-    if (fill && d_nbr == nullptr && tmp.get(&d_nbr, (size_t)T)) return 1;      // the emit pass reads the rows
+    const size_t NQ = (size_t)nq;
+    Pieces pc;
+    pc.add(&d_qkey, NQ), pc.add(&d_qkey_s, NQ), pc.add(&d_qkey_t, NQ), pc.add(&d_qperm, NQ), pc.add(&d_qperm_t, NQ);
+    pc.add(&d_temp, radix::scratch_bytes(nq)), pc.add(&d_count, NQ), pc.add(&d_stat, 3 * NQ), pc.add(&d_stat_part, 3 * (size_t)kStatBlocks);
+    pc.add(&d_tile, (size_t)scan64::tiles(nq) + 1), pc.add(&d_offset, NQ), pc.add(&d_edge_off, (size_t)B + 1), pc.add(&d_wlow, (size_t)B);
+    if (fill && d_nbr == nullptr) pc.add(&d_nbr, (size_t)T);                   // the emit pass reads the rows
+    if (tmp.carve(pc)) return 1;
     AMP_HIP(hipMemcpyAsync(d_wlow, wlow.data(), sizeof(WLow) * (size_t)B, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(knnb_query_key_kernel, dim3(qit.item_blocks), dim3(64 * kItemWaves), 0, st, qit.W, (const int32_t *)qit.d_items,
                        (int)dim, queries_dev, (const Grid *)cg.d_grids, (const uint32_t *)cg.d_cell_base, d_qkey);
@@ -428,9 +429,7 @@ extern "C" int athena_mp_knn_graph_bipartite_host(int32_t n_clouds, int32_t n_qu
     hipStream_t st = amp::stream();
     amp::Scratch tmp;
     float *d_q = nullptr, *d_s = nullptr;
-    if (tmp.get(&d_q, (size_t)n_queries * dim) || tmp.get(&d_s, (size_t)n_sources * dim)) return 1;
-    if (n_queries > 0) AMP_HIP(hipMemcpyAsync(d_q, queries_host, sizeof(float) * (size_t)n_queries * dim, hipMemcpyHostToDevice, st));
-    if (n_sources > 0) AMP_HIP(hipMemcpyAsync(d_s, sources_host, sizeof(float) * (size_t)n_sources * dim, hipMemcpyHostToDevice, st));
+    if (tmp.upload(&d_q, queries_host, (size_t)n_queries * dim, st) || tmp.upload(&d_s, sources_host, (size_t)n_sources * dim, st)) return 1;
     int64_t E = 0;
     if (adj_ja_out == nullptr) {                                  // size query
         if (int rc = amp::knn_pairs_bipartite_core(who, n_clouds, n_queries, query_offsets_host, n_sources, source_offsets_host, dim, d_q, d_s,
@@ -452,9 +451,9 @@ extern "C" int athena_mp_knn_graph_bipartite_host(int32_t n_clouds, int32_t n_qu
     AMP_REQUIRE(adj_ia_out != nullptr && (coords_out != nullptr || E == 0), "%s: null output array", who);
     AMP_REQUIRE(capacity >= E, "%s: adj_ja buffer holds %lld entries, the graph has %lld", who, (long long)capacity, (long long)E);
     AMP_REQUIRE(coords_capacity >= E, "%s: coords buffer holds %lld pairs, the graph has %lld", who, (long long)coords_capacity, (long long)E);
-    if (E > 0) AMP_HIP(hipMemcpyAsync(coords_out, d_coords, sizeof(float) * (size_t)E * dim, hipMemcpyDeviceToHost, st));
-    if (nbr_out && T > 0) AMP_HIP(hipMemcpyAsync(nbr_out, d_nbr, sizeof(int32_t) * (size_t)T, hipMemcpyDeviceToHost, st));
-    if (sqdist_out && T > 0) AMP_HIP(hipMemcpyAsync(sqdist_out, d_sqdist, sizeof(float) * (size_t)T, hipMemcpyDeviceToHost, st));
+    if (tmp.download(coords_out, d_coords, (size_t)E * dim, st) || tmp.download(nbr_out, d_nbr, (size_t)T, st) ||
+        tmp.download(sqdist_out, d_sqdist, (size_t)T, st))
+        return 1;
     int32_t *ja_dev = nullptr;
     std::vector<int32_t> row_deg, col_deg;
     const int rc = amp::bipartite_csr_from_pairs(who, n_queries, n_sources, E, d_pairs, adj_ia_out, adj_ja_out, capacity, &ja_dev, &row_deg,

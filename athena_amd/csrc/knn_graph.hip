@@ -281,16 +281,22 @@ int knn_pairs_batched_core(int32_t B, int32_t n, const int32_t *offsets, int32_t
     const BatchItems &it = cg.it;
     const int64_t T = (int64_t)n * k;
 
+    // the search's arrays, and those of the symmetrisation: one sort of the n k keys, flags, a 64-bit scan in key order
     WLow *d_wlow = nullptr;
     uint32_t *d_stat = nullptr;
-    int32_t *d_nbr = nullptr;
-    unsigned long long *d_stat_part = nullptr;
-    if (tmp.get(&d_wlow, B) || tmp.get(&d_stat, 3 * (size_t)n) || tmp.get(&d_stat_part, 3 * (size_t)kStatBlocks)) return 1;
-    if (nbr_dev == nullptr) {
-        if (tmp.get(&d_nbr, (size_t)T)) return 1;
-    } else {
-        d_nbr = nbr_dev;
-    }
+    int32_t *d_nbr = nbr_dev, *d_v = nullptr, *d_v_t = nullptr;
+    unsigned long long *d_stat_part = nullptr, *d_pk = nullptr, *d_pk_s = nullptr, *d_pk_t = nullptr, *d_tile = nullptr, *d_offset = nullptr;
+    uint8_t *d_flag = nullptr;
+    long long *d_edge_off = nullptr;
+    char *d_temp2 = nullptr;
+    const size_t TT = (size_t)T;
+    Pieces pc;
+    pc.add(&d_wlow, (size_t)B), pc.add(&d_stat, 3 * (size_t)n), pc.add(&d_stat_part, 3 * (size_t)kStatBlocks);
+    if (nbr_dev == nullptr) pc.add(&d_nbr, TT);
+    pc.add(&d_pk, TT), pc.add(&d_pk_s, TT), pc.add(&d_pk_t, TT), pc.add(&d_v, TT), pc.add(&d_v_t, TT), pc.add(&d_flag, TT);
+    pc.add(&d_tile, (size_t)scan64::tiles(T) + 1), pc.add(&d_offset, TT), pc.add(&d_edge_off, (size_t)B + 1);
+    pc.add(&d_temp2, radix::scratch_bytes(T));
+    if (tmp.carve(pc)) return 1;
     AMP_HIP(hipMemcpyAsync(d_wlow, wlow.data(), sizeof(WLow) * (size_t)B, hipMemcpyHostToDevice, st));
     launch_search(dim, n, st, B, (const int32_t *)it.d_off, (const Grid *)cg.d_grids, (const WLow *)d_wlow,
                   (const uint32_t *)cg.d_cell_base, (int)k, r2, (const float *)cg.d_sorted, (const int32_t *)cg.d_perm,
@@ -299,16 +305,6 @@ int knn_pairs_batched_core(int32_t B, int32_t n, const int32_t *offsets, int32_t
     hipLaunchKernelGGL(knn_stat_kernel, dim3(stat_blocks), dim3(256), 0, st, n, (const uint32_t *)d_stat, d_stat_part);
     AMP_LAUNCH_CHECK();
 
-    // symmetrise: one sort of the n k keys, flags, a 64-bit scan in key order
-    unsigned long long *d_pk = nullptr, *d_pk_s = nullptr, *d_pk_t = nullptr, *d_tile = nullptr, *d_offset = nullptr;
-    int32_t *d_v = nullptr, *d_v_t = nullptr;
-    uint8_t *d_flag = nullptr;
-    long long *d_edge_off = nullptr;
-    void *d_temp2 = nullptr;
-    if (tmp.get(&d_pk, T) || tmp.get(&d_pk_s, T) || tmp.get(&d_pk_t, T) || tmp.get(&d_v, T) || tmp.get(&d_v_t, T) || tmp.get(&d_flag, T) ||
-        tmp.get(&d_tile, (size_t)scan64::tiles(T) + 1) || tmp.get(&d_offset, T) || tmp.get(&d_edge_off, (size_t)B + 1) ||
-        tmp.get((char **)&d_temp2, radix::scratch_bytes(T)))
-        return 1;
     const unsigned long long pad = (unsigned long long)n * (unsigned long long)n;
     hipLaunchKernelGGL(knn_pair_key_kernel, dim3(blocks(T)), dim3(256), 0, st, T, n, (int)k, (const int32_t *)d_nbr, d_pk);
     AMP_LAUNCH_CHECK();
@@ -383,8 +379,7 @@ extern "C" int athena_mp_knn_graph_batched_host(int32_t n_clouds, int32_t n, con
     float *d_pts = nullptr, *d_coords = nullptr;
     int32_t *d_pairs = nullptr;
     const int64_t T = (int64_t)n * k;            // always enough: one search, narrowed afterwards
-    if (tmp.get(&d_pts, (size_t)n * dim) || tmp.get(&d_pairs, 2 * (size_t)T) || tmp.get(&d_coords, (size_t)T * dim)) return 1;
-    if (n > 0) AMP_HIP(hipMemcpyAsync(d_pts, points_host, sizeof(float) * (size_t)n * dim, hipMemcpyHostToDevice, st));
+    if (tmp.upload(&d_pts, points_host, (size_t)n * dim, st) || tmp.get(&d_pairs, 2 * (size_t)T) || tmp.get(&d_coords, (size_t)T * dim)) return 1;
     int64_t E = 0;
     if (int rc = amp::knn_pairs_batched_core(n_clouds, n, offsets_host, dim, d_pts, k, radius, mode, nullptr, d_pairs, d_coords, T,
                                              edge_offsets_out, &E))

@@ -249,16 +249,6 @@ struct GrowBuffer {
     }
 };
 
-struct Pieces {
-    size_t total = 0;
-    size_t add(size_t bytes)
-    {
-        const size_t at = total;
-        total += (bytes + 255) & ~(size_t)255;
-        return at;
-    }
-};
-
 double ms_since(std::chrono::steady_clock::time_point t0)
 {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -341,19 +331,15 @@ int count_stretch(const char *who, athena_mp_sampler *p, int32_t m, const int32_
 {
     hipStream_t st = amp::stream();
     const int32_t n = p->n;
-    Pieces pc;
     const size_t M = (size_t)m;
-    const size_t o_cnt = pc.add(4 * M), o_off = pc.add(8 * M), o_tile = pc.add(8 * ((size_t)scan64::tiles(m) + 1)), o_brow = pc.add(4 * (M + 1)),
-                 o_flags = pc.add(16), o_zero = pc.add(8), o_vm = pc.add(4 * M);
-    if (p->head.ensure(pc.total)) return 1;
-    char *base = p->head.ptr;
-    uint32_t *d_cnt = (uint32_t *)(base + o_cnt);
-    unsigned long long *d_off = (unsigned long long *)(base + o_off), *d_tile = (unsigned long long *)(base + o_tile);
-    out->brow = (int32_t *)(base + o_brow);
-    out->flags = (int32_t *)(base + o_flags);
-    out->zero = (unsigned long long *)(base + o_zero);
-    out->seed_vm = (int32_t *)(base + o_vm);
-    AMP_HIP(hipMemsetAsync(base + o_flags, 0, o_zero - o_flags + 8, st));   // the flags and, a piece further, the zero word
+    uint32_t *d_cnt = nullptr;
+    unsigned long long *d_off = nullptr, *d_tile = nullptr;
+    amp::Pieces pc;
+    pc.add(&d_cnt, M), pc.add(&d_off, M), pc.add(&d_tile, (size_t)scan64::tiles(m) + 1), pc.add(&out->brow, M + 1), pc.add(&out->flags, 4);
+    pc.add(&out->zero, 1), pc.add(&out->seed_vm, M);
+    if (p->head.ensure(pc.bytes())) return 1;
+    pc.place(p->head.ptr);
+    AMP_HIP(hipMemsetAsync(out->flags, 0, (char *)out->zero - (char *)out->flags + 8, st));   // the flags and, a piece further, the zero word
     if (p->slot_dirty) {
         AMP_HIP(hipMemsetAsync(p->d_slot, 0xFF, sizeof(int32_t) * (size_t)std::max(n, 1), st));
         p->slot_dirty = false;
@@ -444,19 +430,16 @@ int sample_core(const char *who, athena_mp_sampler *p, int32_t m, const int32_t 
 
     const int draw_blocks = (int)std::min<int64_t>(kDrawMaxBlocks, ((int64_t)m + kDrawWaves - 1) / kDrawWaves);
     const size_t n_waves = (size_t)draw_blocks * kDrawWaves, Nz = (size_t)N, M = (size_t)m;
-    Pieces pc;
-    const size_t o_vm = pc.add(4 * (M + Nz)), o_gcol = pc.add(4 * Nz), o_key = pc.add(4 * Nz), o_key_s = pc.add(4 * Nz), o_key_t = pc.add(4 * Nz),
-                 o_perm = pc.add(4 * Nz), o_perm_t = pc.add(4 * Nz), o_flag = pc.add(4 * Nz), o_before = pc.add(8 * Nz),
-                 o_tile = pc.add(8 * ((size_t)scan64::tiles(N) + 1)), o_temp = pc.add(amp::radix::scratch_bytes(N)), o_ja = pc.add(8 * Nz),
-                 o_cdeg = pc.add(4 * (M + Nz)), o_rdeg = pc.add(4 * M), o_stat = pc.add(16 * n_waves);
-    if (p->body.ensure(pc.total)) return refuse(1);
-    char *base = p->body.ptr;
-    int32_t *d_vm = (int32_t *)(base + o_vm), *d_gcol = (int32_t *)(base + o_gcol), *d_perm = (int32_t *)(base + o_perm),
-            *d_perm_t = (int32_t *)(base + o_perm_t), *d_ja = (int32_t *)(base + o_ja), *d_cdeg = (int32_t *)(base + o_cdeg),
-            *d_rdeg = (int32_t *)(base + o_rdeg);
-    uint32_t *d_key = (uint32_t *)(base + o_key), *d_key_s = (uint32_t *)(base + o_key_s), *d_key_t = (uint32_t *)(base + o_key_t),
-             *d_flag = (uint32_t *)(base + o_flag), *d_stat = (uint32_t *)(base + o_stat);
-    unsigned long long *d_before = (unsigned long long *)(base + o_before), *d_tile = (unsigned long long *)(base + o_tile);
+    int32_t *d_vm = nullptr, *d_gcol = nullptr, *d_perm = nullptr, *d_perm_t = nullptr, *d_ja = nullptr, *d_cdeg = nullptr, *d_rdeg = nullptr;
+    uint32_t *d_key = nullptr, *d_key_s = nullptr, *d_key_t = nullptr, *d_flag = nullptr, *d_stat = nullptr;
+    unsigned long long *d_before = nullptr, *d_tile = nullptr;
+    char *d_temp = nullptr;
+    amp::Pieces pc;
+    pc.add(&d_vm, M + Nz), pc.add(&d_gcol, Nz), pc.add(&d_key, Nz), pc.add(&d_key_s, Nz), pc.add(&d_key_t, Nz), pc.add(&d_perm, Nz);
+    pc.add(&d_perm_t, Nz), pc.add(&d_flag, Nz), pc.add(&d_before, Nz), pc.add(&d_tile, (size_t)scan64::tiles(N) + 1);
+    pc.add(&d_temp, amp::radix::scratch_bytes(N)), pc.add(&d_ja, 2 * Nz), pc.add(&d_cdeg, M + Nz), pc.add(&d_rdeg, M), pc.add(&d_stat, 4 * n_waves);
+    if (p->body.ensure(pc.bytes())) return refuse(1);
+    pc.place(p->body.ptr);
 
     auto body = [&](unsigned long long *n_new) -> int {
         AMP_HIP(hipMemcpyAsync(d_vm, co.seed_vm, 4 * M, hipMemcpyDeviceToDevice, st));   // vm [m + nnz] could not be sized before nnz
@@ -471,7 +454,7 @@ int sample_core(const char *who, athena_mp_sampler *p, int32_t m, const int32_t 
         if (N > 0) {
             hipLaunchKernelGGL(ns_key_kernel, dim3(blocks(N)), dim3(256), 0, st, N, (const int32_t *)d_gcol, (const int32_t *)p->d_slot, n, d_key);
             if (int rc = amp::radix::sort_pairs<uint32_t>((const uint32_t *)d_key, nullptr, N, bits_for((unsigned long long)n), d_key_s, d_perm,
-                                                          d_key_t, d_perm_t, base + o_temp, st))
+                                                          d_key_t, d_perm_t, d_temp, st))
                 return rc;
             hipLaunchKernelGGL(ns_head_flag_kernel, dim3(blocks(N)), dim3(256), 0, st, N, (const uint32_t *)d_key_s, n, d_flag);
             d_new = scan64::exclusive<uint32_t>(N, (const uint32_t *)d_flag, d_tile, d_before, st);
@@ -620,8 +603,7 @@ int athena_mp_sample_neighbors_host(athena_mp_sampler *p, int32_t n_seeds, const
     amp::Scratch tmp;
     const size_t M = (size_t)n_seeds;
     int32_t *d_seeds = nullptr, *d_vm = nullptr, *d_em = nullptr, *d_ed = nullptr;
-    if (tmp.get(&d_seeds, M)) return 1;
-    if (M > 0) AMP_HIP(hipMemcpyAsync(d_seeds, seeds_host, sizeof(int32_t) * M, hipMemcpyHostToDevice, st));
+    if (tmp.upload(&d_seeds, seeds_host, M, st)) return 1;
     if (adj_ja_out == nullptr)                                         // size query
         return sample_core(who, p, n_seeds, d_seeds, k, seed, degree_mode, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, nullptr, n_cols_out,
                            nnz_out, nullptr);
@@ -636,9 +618,7 @@ int athena_mp_sample_neighbors_host(athena_mp_sampler *p, int32_t n_seeds, const
                              adj_ia_out, adj_ja_out, n_cols_out, nnz_out, block))
         return rc;
     const size_t C = (size_t)*n_cols_out, N = (size_t)*nnz_out;
-    if (d_vm && C > 0) AMP_HIP(hipMemcpyAsync(vertex_map_out, d_vm, sizeof(int32_t) * C, hipMemcpyDeviceToHost, st));
-    if (d_em && N > 0) AMP_HIP(hipMemcpyAsync(entry_map_out, d_em, sizeof(int32_t) * N, hipMemcpyDeviceToHost, st));
-    if (d_ed && N > 0) AMP_HIP(hipMemcpyAsync(edge_map_out, d_ed, sizeof(int32_t) * N, hipMemcpyDeviceToHost, st));
+    if (tmp.download(vertex_map_out, d_vm, C, st) || tmp.download(entry_map_out, d_em, N, st) || tmp.download(edge_map_out, d_ed, N, st)) return 1;
     AMP_HIP(hipStreamSynchronize(st));
     return 0;
 }

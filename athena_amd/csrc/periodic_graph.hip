@@ -638,11 +638,14 @@ int periodic_pairs_core(int32_t B, int32_t n, const int32_t *offsets, const floa
         uint32_t *d_ck = nullptr, *d_ck_s = nullptr, *d_ck_t = nullptr, *d_cnt = nullptr;
         int32_t *d_perm = nullptr, *d_perm_t = nullptr, *d_cell_start = nullptr;
         unsigned long long *d_ptile = nullptr;
-        void *d_temp = nullptr;
-        if (tmp.get(&d_gs, (size_t)G + 1) || tmp.get(&d_ck, NG) || tmp.get(&d_ck_s, NG) || tmp.get(&d_ck_t, NG) || tmp.get(&d_perm, NG) ||
-            tmp.get(&d_perm_t, NG) || tmp.get(&d_cell_start, (size_t)NC + 1) || tmp.get(&d_cnt, (size_t)NG + 1) ||
-            tmp.get(&d_ptile, (size_t)scan64::tiles(NG + 1) + 1) || tmp.get(&d_poff, (size_t)NG + 1) || tmp.get((char **)&d_temp, radix::scratch_bytes(NG)))
-            return 1;
+        char *d_temp = nullptr;
+        const size_t NGz = (size_t)NG;
+        Pieces pc;
+        pc.add(&d_gs, (size_t)G + 1), pc.add(&d_ck, NGz), pc.add(&d_ck_s, NGz), pc.add(&d_ck_t, NGz), pc.add(&d_perm, NGz), pc.add(&d_perm_t, NGz);
+        pc.add(&d_cell_start, (size_t)NC + 1), pc.add(&d_cnt, NGz + 1), pc.add(&d_ptile, (size_t)scan64::tiles(NG + 1) + 1);
+        pc.add(&d_poff, NGz + 1);
+        pc.add(&d_temp, radix::scratch_bytes(NG));
+        if (tmp.carve(pc)) return 1;
         AMP_HIP(hipMemcpyAsync(d_gs, gs.data(), sizeof(PgGridS) * ((size_t)G + 1), hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(pg_cell_key_kernel, dim3(blocks(NG)), dim3(256), 0, st, (int32_t)NG, (const PgGridS *)d_gs, G,
                            (const int32_t *)d_off, frac_dev, d_ck);
@@ -672,10 +675,12 @@ int periodic_pairs_core(int32_t B, int32_t n, const int32_t *offsets, const floa
         const int64_t NP = (int64_t)poff[NG];
         unsigned long long *d_pk = nullptr, *d_pk_t = nullptr;
         int32_t *d_v = nullptr, *d_v_t = nullptr;
-        void *d_temp2 = nullptr;
-        if (tmp.get(&d_pk, NP) || tmp.get(&d_key, NP) || tmp.get(&d_pk_t, NP) || tmp.get(&d_v, NP) || tmp.get(&d_v_t, NP) ||
-            tmp.get((char **)&d_temp2, radix::scratch_bytes(NP)))
-            return 1;
+        char *d_temp2 = nullptr;
+        const size_t NPz = (size_t)NP;
+        Pieces pk;
+        pk.add(&d_pk, NPz), pk.add(&d_key, NPz), pk.add(&d_pk_t, NPz), pk.add(&d_v, NPz), pk.add(&d_v_t, NPz);
+        pk.add(&d_temp2, radix::scratch_bytes(NP));
+        if (tmp.carve(pk)) return 1;
         hipLaunchKernelGGL(pg_partner_kernel<true>, dim3(blocks(NG + 1)), dim3(256), 0, st, (int32_t)NG, (const PgGridS *)d_gs, G,
                            (const uint32_t *)d_ck, (const int32_t *)d_perm, (const int32_t *)d_cell_start, (uint32_t *)nullptr,
                            (const unsigned long long *)d_poff, d_pk);
@@ -734,7 +739,9 @@ int periodic_pairs_core(int32_t B, int32_t n, const int32_t *offsets, const floa
     int32_t *d_items = nullptr;
     unsigned long long *d_count = nullptr, *d_tile = nullptr, *d_offset = nullptr;
     const uint32_t tiles = scan64::tiles(W);
-    if (tmp.get(&d_items, items.size()) || tmp.get(&d_count, W) || tmp.get(&d_tile, (size_t)tiles + 1) || tmp.get(&d_offset, W)) return 1;
+    Pieces pw;
+    pw.add(&d_items, items.size()), pw.add(&d_count, (size_t)W), pw.add(&d_tile, (size_t)tiles + 1), pw.add(&d_offset, (size_t)W);
+    if (tmp.carve(pw)) return 1;
     AMP_HIP(hipMemcpyAsync(d_items, items.data(), sizeof(int32_t) * items.size(), hipMemcpyHostToDevice, st));
 
     const PgCand cand = {d_key, d_poff, (unsigned long long)NG, 0};
@@ -836,9 +843,7 @@ extern "C" int athena_mp_periodic_graph_host(int32_t n_structures, int32_t n_ato
     Scratch tmp;
     float *d_frac = nullptr, *d_lat = nullptr, *d_feature = nullptr, *d_vec = nullptr;
     int32_t *d_pairs = nullptr, *d_first = nullptr;
-    if (tmp.get(&d_frac, 3 * (size_t)n) || tmp.get(&d_lat, 9 * (size_t)B)) return 1;
-    if (n > 0) AMP_HIP(hipMemcpyAsync(d_frac, frac_host, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, st));
-    if (B > 0) AMP_HIP(hipMemcpyAsync(d_lat, lat_host, sizeof(float) * 9 * (size_t)B, hipMemcpyHostToDevice, st));
+    if (tmp.upload(&d_frac, frac_host, 3 * (size_t)n, st) || tmp.upload(&d_lat, lat_host, 9 * (size_t)B, st)) return 1;
     int64_t E = 0;
     if (int rc = amp::periodic_pairs_core(B, n, offsets_host, d_frac, d_lat, pbc, cutoff_min, cutoff_max, nullptr, nullptr, nullptr, nullptr,
                                           nullptr, 0, &E, nullptr))
@@ -867,9 +872,9 @@ extern "C" int athena_mp_periodic_graph_host(int32_t n_structures, int32_t n_ato
     if (int rc = amp::csr_from_edges_core(n, E, d_pairs, add_self_loops, ia, adj_ja_out, capacity, &nnz, nullptr, true)) return rc;
     *nnz_out = nnz;
     if (query) return 0;
-    if (d_feature && E > 0) AMP_HIP(hipMemcpyAsync(feature_out, d_feature, sizeof(float) * (size_t)E, hipMemcpyDeviceToHost, st));
-    if (d_vec && E > 0) AMP_HIP(hipMemcpyAsync(vec_out, d_vec, sizeof(float) * 3 * (size_t)E, hipMemcpyDeviceToHost, st));
-    if (d_first && n > 0) AMP_HIP(hipMemcpyAsync(first_count_out, d_first, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, st));
+    if (tmp.download(feature_out, d_feature, (size_t)E, st) || tmp.download(vec_out, d_vec, 3 * (size_t)E, st) ||
+        tmp.download(first_count_out, d_first, (size_t)n, st))
+        return 1;
     AMP_HIP(hipStreamSynchronize(st));
     return 0;
 }

@@ -183,9 +183,9 @@ int radius_pairs_batched_core(const Caller &c, int32_t B, int32_t n, const int32
     uint32_t *d_count = nullptr;
     unsigned long long *d_tile = nullptr, *d_offset = nullptr;
     long long *d_edge_off = nullptr;
-    if (tmp.get(&d_count, n) || tmp.get(&d_tile, (size_t)scan64::tiles(n) + 1) || tmp.get(&d_offset, n) ||
-        tmp.get(&d_edge_off, (size_t)B + 1))
-        return 1;
+    Pieces pc;
+    pc.add(&d_count, (size_t)n), pc.add(&d_tile, (size_t)scan64::tiles(n) + 1), pc.add(&d_offset, (size_t)n), pc.add(&d_edge_off, (size_t)B + 1);
+    if (tmp.carve(pc)) return 1;
     const unsigned long long M = (unsigned long long)cg.it.m_max;
     launch_neighbour<false>(dim, n, st, B, d_off, (const Grid *)cg.d_grids, (const uint32_t *)cg.d_cell_base, M, r2,
                             (const float *)cg.d_sorted, (const int32_t *)cg.d_perm, (const uint32_t *)cg.d_key_s,
@@ -211,10 +211,11 @@ int radius_pairs_batched_core(const Caller &c, int32_t B, int32_t n, const int32
     const int64_t E = (int64_t)total;
     unsigned long long *d_pk = nullptr, *d_pk_s = nullptr, *d_pk_t = nullptr;
     int32_t *d_v = nullptr, *d_v_t = nullptr;
-    void *d_temp2 = nullptr;
-    if (tmp.get(&d_pk, E) || tmp.get(&d_pk_s, E) || tmp.get(&d_pk_t, E) || tmp.get(&d_v, E) || tmp.get(&d_v_t, E) ||
-        tmp.get((char **)&d_temp2, radix::scratch_bytes(E)))
-        return 1;
+    char *d_temp2 = nullptr;
+    const size_t EE = (size_t)E;
+    Pieces pk;
+    pk.add(&d_pk, EE), pk.add(&d_pk_s, EE), pk.add(&d_pk_t, EE), pk.add(&d_v, EE), pk.add(&d_v_t, EE), pk.add(&d_temp2, radix::scratch_bytes(E));
+    if (tmp.carve(pk)) return 1;
     launch_neighbour<true>(dim, n, st, B, d_off, (const Grid *)cg.d_grids, (const uint32_t *)cg.d_cell_base, M, r2,
                            (const float *)cg.d_sorted, (const int32_t *)cg.d_perm, (const uint32_t *)cg.d_key_s,
                            (const int32_t *)cg.d_cell_start, (uint32_t *)nullptr, (const unsigned long long *)d_offset, d_pk);
@@ -265,8 +266,7 @@ extern "C" int athena_mp_radius_graph_host(int32_t n, int32_t dim, const float *
     hipStream_t st = amp::stream();
     Scratch tmp;
     float *d_pts = nullptr;
-    if (tmp.get(&d_pts, (size_t)n * dim)) return 1;
-    if (n > 0) AMP_HIP(hipMemcpyAsync(d_pts, points_host, sizeof(float) * (size_t)n * dim, hipMemcpyHostToDevice, st));
+    if (tmp.upload(&d_pts, points_host, (size_t)n * dim, st)) return 1;
     int64_t E = 0;
     if (int rc = amp::radius_pairs_core(n, dim, d_pts, radius, nullptr, nullptr, 0, &E)) return rc;
     return amp::graph_host_tail("radius_graph_host", n, dim, E, add_self_loops, adj_ia_out, adj_ja_out, capacity, nnz_out, coords_out,
@@ -297,8 +297,7 @@ extern "C" int athena_mp_radius_graph_batched_host(int32_t n_clouds, int32_t n, 
     hipStream_t st = amp::stream();
     Scratch tmp;
     float *d_pts = nullptr;
-    if (tmp.get(&d_pts, (size_t)n * dim)) return 1;
-    if (n > 0) AMP_HIP(hipMemcpyAsync(d_pts, points_host, sizeof(float) * (size_t)n * dim, hipMemcpyHostToDevice, st));
+    if (tmp.upload(&d_pts, points_host, (size_t)n * dim, st)) return 1;
     int64_t E = 0;
     if (int rc = amp::radius_pairs_batched_core(kBatched, n_clouds, n, offsets_host, dim, d_pts, radius, nullptr, nullptr, 0,
                                                 edge_offsets_out, &E))

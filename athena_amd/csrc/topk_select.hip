@@ -44,6 +44,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "call_scratch.h"
 #include "common.h"
 #include "knn_cells.h"
 #include "radix_sort.h"
@@ -285,30 +286,6 @@ int sr_arguments_check(const char *who, int32_t n, int32_t m, int32_t F)
     return 0;
 }
 
-// the word the row kernels leave their smallest refused element in
-struct BadWord {
-    unsigned long long *dev = nullptr;
-    int arm(amp::Scratch &tmp, hipStream_t st)
-    {
-        static const unsigned long long none = ~0ull;
-        if (tmp.get(&dev, 1)) return 1;
-        AMP_HIP(hipMemcpyAsync(dev, &none, sizeof(none), hipMemcpyHostToDevice, st));
-        return 0;
-    }
-    // 0, or 2 with "<who>: <name>(<element>) = <value> outside [lo,hi]"
-    int read(const char *who, const char *name, const int32_t *ids_dev, int32_t lo, int32_t hi, hipStream_t st)
-    {
-        unsigned long long bad = ~0ull;
-        AMP_HIP(hipMemcpyAsync(&bad, dev, sizeof(bad), hipMemcpyDeviceToHost, st));
-        AMP_HIP(hipStreamSynchronize(st));
-        if (bad == ~0ull) return 0;
-        int32_t id = 0;
-        AMP_HIP(hipMemcpy(&id, ids_dev + bad, sizeof(id), hipMemcpyDeviceToHost));
-        amp::set_error("%s: %s(%llu) = %d outside [%d,%d]", who, name, bad + 1, id, lo, hi);
-        return 2;
-    }
-};
-
 } // namespace
 
 namespace amp {
@@ -358,29 +335,20 @@ int topk_vertices_core(const char *who, int32_t B, int32_t n, const int32_t *off
         amin = tk_asc(b);
     }
 
-    // one allocation cut into pieces
-    size_t total = 0;
-    auto piece = [&](size_t bytes) {
-        const size_t at = total;
-        total += (bytes + 255) & ~(size_t)255;
-        return at;
-    };
+    // one allocation cut into pieces (pieces.h); k's piece is there whether or not it is used
     const size_t N = (size_t)n, S = (size_t)ns, NB = (size_t)B;
-    const size_t o_before = piece(8 * N), o_tile = piece(8 * ((size_t)scan64::tiles(n) + 1)), o_key = piece(8 * S), o_key_s = piece(8 * S),
-                 o_key_t = piece(8 * S), o_val = piece(4 * S), o_val_s = piece(4 * S), o_val_t = piece(4 * S), o_flag = piece(4 * N),
-                 o_rank = piece(4 * N), o_off = piece(4 * (NB + 1)), o_gpos = piece(4 * NB), o_k = piece(4 * NB), o_soff = piece(4 * (NB + 1)),
-                 o_temp = piece(ns > 0 ? radix::scratch_bytes(ns) : 0);
+    unsigned long long *d_before = nullptr, *d_tile = nullptr, *d_key = nullptr, *d_key_s = nullptr, *d_key_t = nullptr;
+    int32_t *d_val = nullptr, *d_val_s = nullptr, *d_val_t = nullptr, *d_rank = nullptr, *d_off = nullptr, *d_gpos = nullptr, *d_k = nullptr,
+            *d_soff = nullptr;
+    uint32_t *d_flag = nullptr;
+    char *d_temp = nullptr;
+    Pieces pc;
+    pc.add(&d_before, N), pc.add(&d_tile, (size_t)scan64::tiles(n) + 1), pc.add(&d_key, S), pc.add(&d_key_s, S), pc.add(&d_key_t, S);
+    pc.add(&d_val, S), pc.add(&d_val_s, S), pc.add(&d_val_t, S), pc.add(&d_flag, N), pc.add(&d_rank, N), pc.add(&d_off, NB + 1);
+    pc.add(&d_gpos, NB), pc.add(&d_k, NB), pc.add(&d_soff, NB + 1), pc.add(&d_temp, ns > 0 ? radix::scratch_bytes(ns) : 0);
     Scratch tmp;
-    char *base = nullptr;
-    if (tmp.get(&base, total)) return 1;
-    unsigned long long *d_before = (unsigned long long *)(base + o_before), *d_tile = (unsigned long long *)(base + o_tile),
-                       *d_key = (unsigned long long *)(base + o_key), *d_key_s = (unsigned long long *)(base + o_key_s),
-                       *d_key_t = (unsigned long long *)(base + o_key_t);
-    int32_t *d_val = (int32_t *)(base + o_val), *d_val_s = (int32_t *)(base + o_val_s), *d_val_t = (int32_t *)(base + o_val_t),
-            *d_rank = (int32_t *)(base + o_rank), *d_off = (int32_t *)(base + o_off), *d_gpos = (int32_t *)(base + o_gpos),
-            *d_k = kk ? (int32_t *)(base + o_k) : nullptr, *d_soff = (int32_t *)(base + o_soff);
-    uint32_t *d_flag = (uint32_t *)(base + o_flag);
-    void *d_temp = base + o_temp;
+    if (tmp.carve(pc)) return 1;
+    if (!kk) d_k = nullptr;
 
     hipStream_t st = stream();
     AMP_HIP(hipMemcpyAsync(d_off, off, sizeof(int32_t) * (NB + 1), hipMemcpyHostToDevice, st));
@@ -494,18 +462,17 @@ extern "C" int athena_mp_topk_vertices_host(int32_t n_graphs, int32_t n, const i
     const size_t N = (size_t)n, R = (size_t)room;
     float *d_score = nullptr;
     int32_t *d_cluster = nullptr, *d_selected = nullptr, *d_order = nullptr;
-    if (tmp.get(&d_score, N) || (cluster_out && tmp.get(&d_cluster, N)) || (selected_out && tmp.get(&d_selected, R)) ||
+    if (tmp.upload(&d_score, score, N, st) || (cluster_out && tmp.get(&d_cluster, N)) || (selected_out && tmp.get(&d_selected, R)) ||
         (order_out && tmp.get(&d_order, R)))
         return 1;
-    if (n > 0) AMP_HIP(hipMemcpyAsync(d_score, score, sizeof(float) * N, hipMemcpyHostToDevice, st));
     int64_t m = 0;
     if (int rc = amp::topk_vertices_core(who, n_graphs, n, offsets, d_score, k, k_each, has_min_score, min_score, d_cluster, d_selected, d_order,
                                          sel_offsets_out, &m))
         return rc;
     *n_selected_out = m;
-    if (d_cluster && n > 0) AMP_HIP(hipMemcpyAsync(cluster_out, d_cluster, sizeof(int32_t) * N, hipMemcpyDeviceToHost, st));
-    if (d_selected && m > 0) AMP_HIP(hipMemcpyAsync(selected_out, d_selected, sizeof(int32_t) * (size_t)m, hipMemcpyDeviceToHost, st));
-    if (d_order && m > 0) AMP_HIP(hipMemcpyAsync(order_out, d_order, sizeof(int32_t) * (size_t)m, hipMemcpyDeviceToHost, st));
+    if (tmp.download(cluster_out, d_cluster, N, st) || tmp.download(selected_out, d_selected, (size_t)m, st) ||
+        tmp.download(order_out, d_order, (size_t)m, st))
+        return 1;
     AMP_HIP(hipStreamSynchronize(st));
     return 0;
 }
@@ -540,12 +507,10 @@ extern "C" int athena_mp_select_rows_host(int32_t n, int32_t m, int32_t F, const
     const size_t N = (size_t)n, M = (size_t)m, W = (size_t)F;
     int32_t *d_sel = nullptr;
     float *d_x = nullptr, *d_gate = nullptr, *d_y = nullptr;
-    if (tmp.get(&d_sel, M) || tmp.get(&d_x, N * W) || (gate && tmp.get(&d_gate, N)) || tmp.get(&d_y, M * W)) return 1;
-    AMP_HIP(hipMemcpyAsync(d_sel, selected, sizeof(int32_t) * M, hipMemcpyHostToDevice, st));
-    if (n > 0) AMP_HIP(hipMemcpyAsync(d_x, x, sizeof(float) * N * W, hipMemcpyHostToDevice, st));
-    if (gate && n > 0) AMP_HIP(hipMemcpyAsync(d_gate, gate, sizeof(float) * N, hipMemcpyHostToDevice, st));
+    if (tmp.upload(&d_sel, selected, M, st) || tmp.upload(&d_x, x, N * W, st) || (gate && tmp.upload(&d_gate, gate, N, st)) || tmp.get(&d_y, M * W))
+        return 1;
     if (int rc = amp::select_rows_fwd_core(who, n, m, F, d_sel, d_x, d_gate, d_y)) return rc;
-    AMP_HIP(hipMemcpyAsync(y, d_y, sizeof(float) * M * W, hipMemcpyDeviceToHost, st));
+    if (tmp.download(y, d_y, M * W, st)) return 1;
     AMP_HIP(hipStreamSynchronize(st));
     return 0;
 }
@@ -564,16 +529,11 @@ extern "C" int athena_mp_select_rows_bwd_host(int32_t n, int32_t m, int32_t F, c
     const size_t N = (size_t)n, M = (size_t)m, W = (size_t)F;
     int32_t *d_cluster = nullptr;
     float *d_dy = nullptr, *d_x = nullptr, *d_gate = nullptr, *d_dx = nullptr, *d_dgate = nullptr;
-    if (tmp.get(&d_cluster, N) || tmp.get(&d_dy, M * W) || (dgate && tmp.get(&d_x, N * W)) || (gate && tmp.get(&d_gate, N)) ||
-        (dx && tmp.get(&d_dx, N * W)) || (dgate && tmp.get(&d_dgate, N)))
+    if (tmp.upload(&d_cluster, cluster, N, st) || tmp.upload(&d_dy, dy, M * W, st) || (dgate && tmp.upload(&d_x, x, N * W, st)) ||
+        (gate && tmp.upload(&d_gate, gate, N, st)) || (dx && tmp.get(&d_dx, N * W)) || (dgate && tmp.get(&d_dgate, N)))
         return 1;
-    AMP_HIP(hipMemcpyAsync(d_cluster, cluster, sizeof(int32_t) * N, hipMemcpyHostToDevice, st));
-    if (m > 0) AMP_HIP(hipMemcpyAsync(d_dy, dy, sizeof(float) * M * W, hipMemcpyHostToDevice, st));
-    if (d_x) AMP_HIP(hipMemcpyAsync(d_x, x, sizeof(float) * N * W, hipMemcpyHostToDevice, st));
-    if (d_gate) AMP_HIP(hipMemcpyAsync(d_gate, gate, sizeof(float) * N, hipMemcpyHostToDevice, st));
     if (int rc = amp::select_rows_bwd_core(who, n, m, F, d_cluster, d_dy, d_x, d_gate, d_dx, d_dgate)) return rc;
-    if (d_dx) AMP_HIP(hipMemcpyAsync(dx, d_dx, sizeof(float) * N * W, hipMemcpyDeviceToHost, st));
-    if (d_dgate) AMP_HIP(hipMemcpyAsync(dgate, d_dgate, sizeof(float) * N, hipMemcpyDeviceToHost, st));
+    if (tmp.download(dx, d_dx, N * W, st) || tmp.download(dgate, d_dgate, N, st)) return 1;
     AMP_HIP(hipStreamSynchronize(st));
     return 0;
 }

@@ -39,6 +39,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "cell_start.h"
 #include "common.h"
 #include "row_groups.h"
 #include "scan64.h"
@@ -50,8 +51,6 @@ constexpr uint32_t kItemPairs = 4096;           // pairs per work item of the fi
 constexpr int kFillWaves = 4;                   // work items per 256-thread block
 
 int64_t g_stats[3] = {0, 0, 0};                 // triplets, participants, longest run of the last build
-
-inline unsigned blocks(int64_t n, int per = 256) { return (unsigned)((n + per - 1) / per); }
 
 // the participants of every row: their entry ids compacted to part[rowptr[i] ..], their number m[i], the run m (m - 1) and its work
 // items; rank[k] (may be null) = the participants of the row before entry k
@@ -357,11 +356,12 @@ extern "C" int athena_mp_triplet_pairs(const athena_mp_graph *g, int32_t dim, co
     int32_t *d_part = nullptr, *d_rank = nullptr, *d_m = nullptr;
     uint32_t *d_items = nullptr;
     unsigned long long *d_run = nullptr, *d_tile = nullptr, *d_run_off = nullptr, *d_tile2 = nullptr, *d_item_off = nullptr, *d_four = nullptr;
-    const size_t tiles = (size_t)scan64::tiles(n) + 1;
-    if (tmp.get(&d_part, nnz) || tmp.get(&d_m, n) || tmp.get(&d_items, n) || tmp.get(&d_run, n) || tmp.get(&d_tile, tiles) ||
-        tmp.get(&d_run_off, n) || tmp.get(&d_tile2, tiles) || tmp.get(&d_item_off, n) || tmp.get(&d_four, 4))
-        return 1;
-    if (rowptr_dev && tmp.get(&d_rank, nnz)) return 1;
+    const size_t tiles = (size_t)scan64::tiles(n) + 1, N = (size_t)n;
+    amp::Pieces pc;
+    pc.add(&d_part, (size_t)nnz), pc.add(&d_m, N), pc.add(&d_items, N), pc.add(&d_run, N), pc.add(&d_tile, tiles), pc.add(&d_run_off, N);
+    pc.add(&d_tile2, tiles), pc.add(&d_item_off, N), pc.add(&d_four, 4);
+    if (rowptr_dev) pc.add(&d_rank, (size_t)nnz);
+    if (tmp.carve(pc)) return 1;
     hipLaunchKernelGGL(trip_count_kernel, amp::group_grid(n, kG), dim3(256), 0, st, n, (const int32_t *)g->rowptr, (const int32_t *)g->eid, dim,
                        vec_dev, cutoff3, all, d_part, d_rank, d_m, d_run, d_items);
     const unsigned long long *d_total = scan64::exclusive(n, (const unsigned long long *)d_run, d_tile, d_run_off, st);
@@ -484,10 +484,7 @@ extern "C" int athena_mp_triplets_host(const athena_mp_graph *g, int32_t dim, co
     amp::Scratch tmp;
     const int64_t E = g->n_edge_cols, nnz = g->nnz;
     float *d_vec = nullptr;
-    if (vec && E > 0) {
-        if (tmp.get(&d_vec, (size_t)E * dim)) return 1;
-        AMP_HIP(hipMemcpyAsync(d_vec, vec, sizeof(float) * (size_t)E * dim, hipMemcpyHostToDevice, st));
-    }
+    if (vec && E > 0 && tmp.upload(&d_vec, vec, (size_t)E * dim, st)) return 1;
     int64_t T = 0;
     if (int rc = athena_mp_triplet_pairs(g, dim, d_vec, cutoff3, nullptr, 0, nullptr, &T)) return rc;
     *n_triplets_out = T;
@@ -500,10 +497,10 @@ extern "C" int athena_mp_triplets_host(const athena_mp_graph *g, int32_t dim, co
         float *d_dir = nullptr, *d_cos = nullptr;
         if (tmp.get(&d_dir, (size_t)nnz * dim) || tmp.get(&d_cos, (size_t)T)) return 1;
         if (int rc = athena_mp_entry_vectors_fwd(g, dim, d_vec, d_dir)) return rc;
-        if (dir_out) AMP_HIP(hipMemcpyAsync(dir_out, d_dir, sizeof(float) * (size_t)nnz * dim, hipMemcpyDeviceToHost, st));
+        if (tmp.download(dir_out, d_dir, (size_t)nnz * dim, st)) return 1;
         if (cos_out && T > 0) {
             if (int rc = athena_mp_triplet_cos_fwd(h.tg, dim, d_dir, d_cos)) return rc;
-            AMP_HIP(hipMemcpyAsync(cos_out, d_cos, sizeof(float) * (size_t)T, hipMemcpyDeviceToHost, st));
+            if (tmp.download(cos_out, d_cos, (size_t)T, st)) return 1;
         }
     }
     AMP_HIP(hipStreamSynchronize(st));
@@ -520,8 +517,7 @@ extern "C" int athena_mp_triplet_cos_bwd_host(const athena_mp_graph *g, int32_t 
     hipStream_t st = amp::stream();
     amp::Scratch tmp;
     float *d_vec = nullptr, *d_dir = nullptr, *d_cos = nullptr, *d_dcos = nullptr, *d_ddir = nullptr, *d_dvec = nullptr;
-    if (tmp.get(&d_vec, (size_t)E * dim)) return 1;
-    AMP_HIP(hipMemcpyAsync(d_vec, vec, sizeof(float) * (size_t)E * dim, hipMemcpyHostToDevice, st));
+    if (tmp.upload(&d_vec, vec, (size_t)E * dim, st)) return 1;
     int64_t T = 0;
     if (int rc = athena_mp_triplet_pairs(g, dim, d_vec, cutoff3, nullptr, 0, nullptr, &T)) return rc;
     AMP_REQUIRE(n_triplets == T, "triplet_cos_bwd_host: dcos holds %lld triplets, the graph has %lld", (long long)n_triplets, (long long)T);
@@ -529,15 +525,14 @@ extern "C" int athena_mp_triplet_cos_bwd_host(const athena_mp_graph *g, int32_t 
     std::vector<int32_t> ia((size_t)nnz + 1);
     HandleGuard h;
     if (int rc = build_triplet_handle("triplet_cos_bwd_host", g, dim, d_vec, cutoff3, T, tmp, ia.data(), nullptr, 0, &h.tg)) return rc;
-    if (tmp.get(&d_dir, (size_t)nnz * dim) || tmp.get(&d_cos, (size_t)T) || tmp.get(&d_dcos, (size_t)T) || tmp.get(&d_ddir, (size_t)nnz * dim) ||
-        tmp.get(&d_dvec, (size_t)E * dim))
+    if (tmp.get(&d_dir, (size_t)nnz * dim) || tmp.get(&d_cos, (size_t)T) || tmp.upload(&d_dcos, dcos, (size_t)T, st) ||
+        tmp.get(&d_ddir, (size_t)nnz * dim) || tmp.get(&d_dvec, (size_t)E * dim))
         return 1;
-    if (T > 0) AMP_HIP(hipMemcpyAsync(d_dcos, dcos, sizeof(float) * (size_t)T, hipMemcpyHostToDevice, st));
     if (int rc = athena_mp_entry_vectors_fwd(g, dim, d_vec, d_dir)) return rc;
     if (int rc = athena_mp_triplet_cos_fwd(h.tg, dim, d_dir, d_cos)) return rc;
     if (int rc = athena_mp_triplet_cos_bwd(h.tg, dim, d_dir, d_cos, d_dcos, d_ddir)) return rc;
     if (int rc = athena_mp_entry_vectors_bwd(g, dim, d_ddir, d_dvec)) return rc;
-    AMP_HIP(hipMemcpyAsync(dvec_out, d_dvec, sizeof(float) * (size_t)E * dim, hipMemcpyDeviceToHost, st));
+    if (tmp.download(dvec_out, d_dvec, (size_t)E * dim, st)) return 1;
     AMP_HIP(hipStreamSynchronize(st));
     return 0;
 }

@@ -21,7 +21,25 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RUNNER = os.path.join(ROOT, "athena_amd", "fortran", "contract_run")
 vp = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
 ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-CASES = cr.shape_cases()
+
+
+def _longest_row_cases():
+    """exactly P coarse pairs, P round one block of the longest-row reduction and one past its 512 blocks of 256 rows (the grid-stride
+    loop wraps), all of one member but one of three: the first, the last, and 1-based row 131 072, the last of the first sweep.
+    The chain i -- i + 1 under the identity map; P = 0 is "every edge dropped" of the shared cases"""
+    cases = []
+    for P in (1, 255, 256, 257, 131073):
+        chain = np.stack([np.arange(1, P + 1), np.arange(2, P + 2)], axis=1)
+        for where, row in (("first", 0), ("last", P - 1), ("row 131072", 131071)):
+            if row >= P or (where != "first" and row == 0):
+                continue
+            pairs = np.concatenate([chain, chain[[row, row]][:, ::-1]]).astype(np.int32)          # twice more, given high-low
+            cases.append((f"longest row {where} of {P}", dict(pairs=pairs, n_rows=P + 1, n_cols=P + 1, row_cluster=None, col_cluster=None,
+                                                               m_rows=P + 1, m_cols=P + 1, mode=0, row_points=None, col_points=None)))
+    return tuple(cases)
+
+
+CASES = cr.shape_cases() + _longest_row_cases()
 NAMES = [c[0] for c in CASES]
 
 

@@ -21,7 +21,25 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RUNNER = os.path.join(ROOT, "athena_amd", "fortran", "grid_clusters_run")
 vp = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
 ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-CASES = gr.shape_cases()
+
+
+def _longest_row_cases():
+    """exactly m clusters, m round one block of the longest-row reduction and one past its 512 blocks of 256 rows (the grid-stride
+    loop wraps), all of one point but one of three: the first, the last, and 1-based row 131 072, the last of the first sweep.
+    One cloud on a line, cell i at i + 1/4 (exact in float32), the cloud's corner at 0"""
+    cases = []
+    for m in (1, 255, 256, 257, 131073):
+        line = np.arange(m, dtype=np.float64) + 0.25
+        line[0] = 0.0
+        for where, row in (("first", 0), ("last", m - 1), ("row 131072", 131071)):
+            if row >= m or (where != "first" and row == 0):
+                continue
+            p = np.concatenate([line, [row + 0.5, row + 0.75]]).astype(np.float32)[:, None]
+            cases.append((f"longest row {where} of {m}", np.ascontiguousarray(p), gr.offsets_of([m + 2]), 1.0, None))
+    return cases
+
+
+CASES = gr.shape_cases() + _longest_row_cases()
 NAMES = [c[0] for c in CASES]
 DEVICE_KEYS = ("cluster", "pairs", "rowptr", "weights", "centroid", "nearest", "cell")
 
